@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — agent-steps/sec of the batched step engine on MarlGrid-3AgentCluttered15x15-v0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-per-gpu B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-per-gpu B] [--dump-outputs DIR] [--full]
 
 A "step" is one `env.step(actions)` over the whole per-GPU batch: ONE launch on one stream — mg_step_render:
 the action loop, the reset of every env whose episode just ended and the observation raster in one kernel —
@@ -12,21 +12,26 @@ GPU, RCCL control plane) unless it is already running under a launcher (WORLD_SI
 JSON line.
 
 How the line is measured (one self-consistent measurement, not a collage):
-  * after W warm-up steps, BLOCKS of exactly K steps are timed, each bracketed by barrier + synchronize on
-    both sides and MAX-reduced over ranks, until >= --min-seconds of timed steps (the driver's K = 20 is
-    3.5 ms: far below what clocks and samplers resolve).  `ms_per_step` and `value` are the SUSTAINED rate
-    over all plain blocks — total steps / total time, nothing dropped: every env of this workload runs into
-    max_steps together, so one step in 100 resets the whole batch inside the launch and costs twice the
-    others.  The median block (which hides those steps) is `value_median_block`; min / max / first / last
-    and the blocks beyond 3x the median (`outliers`) are listed.
-  * EVERY block carries two HIP events on the launch stream — before its first launch and after its last (an
-    event costs ~2 us of stream time: 0.1 % of a 20-step block) — so a block's launch interval (GPU span / K:
-    launch + dispatch gap) and its host-timed ms per step describe the same K launches.  `kernels` /
-    `roofline.kernel_ms` report the MEDIAN block, with mean / min / max and the blocks beyond 3x the median
-    (`outliers`) beside it; `closure` = that median / the median host-timed ms per step.
-  * `clocks` holds rocm-smi samples before the first and after the last block; `roofline.traffic`
-    is measured in this run (tools/pmc.py: rocprofv3 --pmc passes in a child process, N = 1 only).
-  * `extra.strong_n1`: the full headline batch (262 144 envs) on ONE GPU, same fields.
+  * after W warm-up steps, exactly K steps are timed as ONE block, bracketed by barrier + synchronize on both
+    sides and MAX-reduced over ranks.  `ms_per_step` and `value` are the SUSTAINED rate over the block — total
+    steps / total time, nothing dropped: every env of this workload runs into max_steps together, so one step
+    in 100 resets the whole batch inside the launch and costs twice the others (a block that holds no such
+    step is that much faster: pick K and W with it in mind when comparing lines).
+  * the block carries two HIP events on the launch stream — before its first launch and after its last (an
+    event costs ~2 us of stream time) — so its launch interval (GPU span / K: launch + dispatch gap) and its
+    host-timed ms per step describe the same K launches: `kernels`, and `closure` = their ratio.
+  * `--dump-outputs DIR`: after the timed block, what the last timed step handed its caller is written to DIR
+    as .npy (float32): rewards (B, n) and done (B,) whole, the observations of a fixed, seeded sample of the
+    envs (`obs_env_ids`) — at most 64 MB in all.  Inputs (seeds, actions) depend only on the arguments, so two
+    builds can be compared output for output.
+  * the interpreter's garbage is collected (and the survivors frozen) before every timed region: a full collection in
+    the middle of a 20-step block is a 50 ms host stall (settle_interpreter).
+A plain run does only that: set up, warm up, time the K steps, dump, print the line.  Everything else is `--full`:
+  * `clocks` holds rocm-smi samples before and after the timed block; `roofline.traffic` is measured in this
+    run (tools/pmc.py: rocprofv3 --pmc passes in a child process, N = 1 only), `roofline.raster_only_ms` by
+    the raster launched alone.
+  * `extra.strong_n1`: the full headline batch (262 144 envs) on ONE GPU, same fields (K-step blocks until
+    min(--min-seconds, 1 s) is timed, as for the two legs below).
   * `extra.step_with_encode`: the step with `MultiGrid.encode` of the batch written by its own launch, against the step alone.
   * `extra.pipelined_shards`: the per-GPU batch (and twice it) as TWO envs on two streams, stepped without a join
     (marlgrid_amd.sharding.ShardPipeline): what overlapping launches of independent shards are worth, next to the
@@ -35,9 +40,8 @@ How the line is measured (one self-consistent measurement, not a collage):
     (child process; the checker, never the thing measured) with the very actions the bench fed them — reset, the W
     warm-up steps and every timed step, auto-reset on `done` — and grid, agent records (stack order included), step
     counter, MT19937 state, the last step's rewards / done and the last observations are compared: the state the
-    timed ~60 000 steps per env end in is the reference's (marlgrid/base.py:501-653 over ~600 episodes per env).
-  * the interpreter's garbage is collected (and the survivors frozen) before every timed region: a full collection in
-    the middle of a 20-step block is a 50 ms host stall (settle_interpreter).
+    timed steps end in is the reference's (marlgrid/base.py:501-653).
+  * `cpu_baseline`: the CPU oracle on the same workload, on the host's cores (child process).
 The run refuses to start if an MG_* / MARLGRID_* environment variable is set, and echoes the
 library's build id.
 """
@@ -473,6 +477,7 @@ def measure(wl, B, dev, ctl, seeds, K, Wm, min_seconds, max_blocks, action_seed,
                           min_seconds, max_blocks, probes)
     env._probe = None
     env.check_errors()
+    env.last_step = last[0]
     if snapshot:
         env.parity_snapshot = parity_snapshot(env, wl, seeds, pool, Wm + len(blocks) * K, last[0])
     return env, summarise(blocks, K), blocks
@@ -514,6 +519,48 @@ def measure_pipeline(wl, B, parts, dev, ctl, K, Wm, min_seconds, max_blocks, act
     if placement:
         placement[0]["placement_retries"] = retries
     return n, summarise(blocks, K), placement
+
+
+DUMP_BYTES = 60 * 1000 * 1000        # --dump-outputs: what the files may hold in all (headers aside), below 64 MB
+
+
+def _output_tensors(x, name):
+    """(name, tensor) of what a step handed back: the tensor itself, or one per agent / 'rich' field"""
+    import torch
+    if torch.is_tensor(x):
+        yield name, x
+    elif isinstance(x, dict):
+        for k in sorted(x):
+            for item in _output_tensors(x[k], "%s_%s" % (name, k)):
+                yield item
+    elif isinstance(x, (list, tuple)):
+        for k, v in enumerate(x):
+            for item in _output_tensors(v, "%s_agent%d" % (name, k)):
+                yield item
+
+
+def dump_outputs(out_dir, batch, step_out):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files in `out_dir` — rewards (B, n) and
+    done (B,) whole, and the observations of a fixed sample of the envs (RandomState(0): the same envs for the same batch),
+    as many as fit DUMP_BYTES with the rest, with their ids (obs_env_ids, float64).  Returns the files written."""
+    import numpy as np
+    import torch
+    obs, rew, done, _ = step_out
+    whole = {"rewards": rew, "done": done}
+    sampled = list(_output_tensors(obs, "obs"))
+    fixed = sum(t.numel() * 4 for t in whole.values())
+    per_env = sum(t[0].numel() * 4 for _, t in sampled) + 8
+    S = max(1, min(batch, (DUMP_BYTES - fixed) // per_env))
+    ids = np.sort(np.random.RandomState(0).choice(batch, S, replace=False))
+    arrays = {k: t.float().cpu().numpy() for k, t in whole.items()}
+    ix = torch.as_tensor(ids, device=sampled[0][1].device)
+    for k, t in sampled:
+        arrays[k] = t.index_select(0, ix).float().cpu().numpy()
+    arrays["obs_env_ids"] = ids.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(k + ".npy" for k in arrays)
 
 
 def raster_only_ms(env, iters=50):
@@ -560,9 +607,15 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch-per-gpu", type=int, default=32768)
-    ap.add_argument("--min-seconds", type=float, default=10.0, help="keep timing K-step blocks until this much is timed "
-                    "(10 s of back-to-back blocks: long enough for clocks and any utilisation sampler to see the card busy)")
+    ap.add_argument("--min-seconds", type=float, default=10.0, help="--full's other timed legs (strong_n1, pipelined_shards): "
+                    "K-step blocks until min(this, 1 s) is timed (--selftest-cpu: until this); the headline is exactly K steps")
     ap.add_argument("--max-blocks", type=int, default=6000)
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline line: clocks, "
+                    "PMC traffic and roofline, extra.* legs, parity_after_timed, cpu_baseline (off: set up, warm up, time the "
+                    "K steps, dump the outputs if asked, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rewards, done, a seeded sample of the "
+                         "observations) to DIR/<name>.npy in float32 (rank 0's shard)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline.traffic = null)")
@@ -642,15 +695,18 @@ def main():
     # the env batch shards embarrassingly: rank r owns global envs [r*B, (r+1)*B), seeds 1337 + id
     seeds = sharding.shard_seeds(1337, B * n_gpus, rank, n_gpus)
     assert len(seeds) == B
-    clocks_before = smi.sample(dev_index) if rank == 0 else None
+    clocks_before = smi.sample(dev_index) if rank == 0 and args.full else None
     fused = not args.unfused
-    env, summary, blocks = measure(wl, B, dev, ctl, seeds, K, Wm, args.min_seconds, args.max_blocks, rank, fused, share,
-                                   snapshot=not args.no_parity)
-    clocks_after = smi.sample(dev_index) if rank == 0 else None
+    check_parity = args.full and not args.no_parity
+    # the headline: exactly K timed steps, one block
+    env, summary, blocks = measure(wl, B, dev, ctl, seeds, K, Wm, 0.0, 1, rank, fused, share, snapshot=check_parity)
+    clocks_after = smi.sample(dev_index) if rank == 0 and args.full else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, B, env.last_step)
     # every rank replays eight envs of ITS shard on the CPU oracle (a child process each, a few seconds, GPUs idle)
-    parity = None if args.no_parity else parity_after_timed(env.parity_snapshot)
-    parity_by_rank = ctl.gather_objects(parity)
-    raster_ms = raster_only_ms(env) if rank == 0 else None
+    parity = parity_after_timed(env.parity_snapshot) if check_parity else None
+    parity_by_rank = ctl.gather_objects(parity) if check_parity else None
+    raster_ms = raster_only_ms(env) if rank == 0 and args.full else None
     # who ran what: every rank's device and its own K-step times (a straggler, or two ranks on one GPU, shows)
     own = robust([b["per_rank_s"][rank] / K * 1e3 for b in blocks if not b["instrumented"]])
     place = getattr(env._groups[0], "placement_ms", None) or {}
@@ -679,7 +735,7 @@ def main():
             "n_gpus": n_gpus, "steps": K, "warmup": Wm,
             "ms_per_step": ms,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "u8", "data": "synthetic",
+            "dtype": "u8", "data": "synthetic", "full": bool(args.full),
             "value_median_block": n_gpus * B * n / (pl["median"] * 1e-3),
             "ms_per_step_median_block": pl["median"],
             "config": {"workload": wl, "batch_per_gpu": B, "global_batch": B * n_gpus, "n_agents": n,
@@ -691,10 +747,10 @@ def main():
                                                             "mg_render_obs"]),
                        "sharding": "env batch split contiguously, no collectives",
                        "obs_buffers": OBS_BUFFERS_NOTE.get(env.place_obs, str(env.place_obs))},
-            "timing": {"what": "K-step blocks, each bracketed by barrier + synchronize; a block's time = MAX over ranks of "
-                               "the rank's own K steps (opening barrier -> its own synchronize; `with_barrier` = up to the "
-                               "end of the closing barrier); value = all plain blocks' steps / their total time (every "
-                               "100th step resets the whole batch in-launch: the median block hides those)",
+            "timing": {"what": "exactly K steps after the W warm-up steps, one block bracketed by barrier + synchronize; its "
+                               "time = MAX over ranks of the rank's own K steps (opening barrier -> its own synchronize; "
+                               "`with_barrier` = up to the end of the closing barrier); value = K steps / that time (every "
+                               "100th step resets the whole batch in-launch: those that fall in the block are in it)",
                        "blocks": pl, "with_barrier": summary["with_barrier"],
                        "value_with_barrier": n_gpus * B * n / (summary["with_barrier"]["mean"] * 1e-3),
                        "seconds_timed": summary["seconds_timed"],
@@ -705,14 +761,15 @@ def main():
                        "launched_by": os.environ.get("BENCH_SELF_LAUNCHED", "external launcher" if world > 1 else "direct")},
             "kernels": summary.get("kernels"),
             "closure": summary.get("closure"),
-            "clocks": {"before": clocks_before, "after": clocks_after, "source": "rocm-smi"},
             "library": build_info,
             "obs_placement": getattr(env._groups[0], "placement_ms", None),
             # every rank's buffers, at the top of the line: a rank off the fast class shows before anyone reads a scaling curve
             "obs_placement_found_by_rank": [r["obs_placement"].get("found") for r in ranks_info],
             "placement_retries_by_rank": [r["placement_retries"] for r in ranks_info],
         }
-        if not args.no_parity:
+        if args.full:
+            out["clocks"] = {"before": clocks_before, "after": clocks_after, "source": "rocm-smi"}
+        if check_parity:
             p0 = parity_by_rank[0] or {}
             out["parity_after_timed"] = dict(p0, ok=all(bool(p and p.get("ok")) for p in parity_by_rank),
                                              ok_by_rank=[bool(p and p.get("ok")) for p in parity_by_rank],
@@ -740,15 +797,15 @@ def main():
             return None
 
     traffic = None
-    if rank == 0 and n_gpus > 1 and not args.no_pmc:
+    if rank == 0 and args.full and n_gpus > 1 and not args.no_pmc:
         traffic = {"skipped": "N > 1: the counters are per process and the other ranks' processes hold their GPUs; the "
                               "per-GPU workload is the N = 1 line's, whose traffic is measured there"}
-    if rank == 0 and n_gpus == 1 and not args.no_pmc:
+    if rank == 0 and args.full and n_gpus == 1 and not args.no_pmc:
         def _pmc():
             import pmc
             return pmc.measure(wl, B)
         traffic = leg("pmc", _pmc)
-    if rank == 0:
+    if rank == 0 and args.full:
         # roofline needs the env's geometry only
         class _Geo(object):
             view_size, tile_size, num_agents, kernel_name = vs, ts, n, kname0
@@ -771,7 +828,7 @@ def main():
         torch.cuda.empty_cache()
         return res
 
-    if n_gpus == 1 and not args.no_strong and wl == WORKLOAD:
+    if args.full and n_gpus == 1 and not args.no_strong and wl == WORKLOAD:
         res = leg("strong_n1", _strong)
         if res is not None:
             out.setdefault("extra", {})["strong_n1"] = res
@@ -796,7 +853,7 @@ def main():
             torch.cuda.empty_cache()
         return pts
 
-    pts = leg("pipelined_shards", _pipeline) if (n_gpus == 1 and not args.no_pipeline and wl == WORKLOAD) else None
+    pts = leg("pipelined_shards", _pipeline) if (args.full and n_gpus == 1 and not args.no_pipeline and wl == WORKLOAD) else None
     if pts:
         out.setdefault("extra", {})["pipelined_shards"] = {
             "what": "the per-GPU batch as TWO envs on two streams — make(id, pipeline=2), stepped part after part with "
@@ -852,13 +909,13 @@ def main():
         torch.cuda.empty_cache()
         return res
 
-    if n_gpus == 1 and not args.no_encode_leg and wl == WORKLOAD:
+    if args.full and n_gpus == 1 and not args.no_encode_leg and wl == WORKLOAD:
         res = leg("step_with_encode", _with_encode)
         if res is not None:
             out.setdefault("extra", {})["step_with_encode"] = res
 
     if rank == 0:
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # rank 0, once, for every N (the other ranks wait in the closing barrier and leave the host cores alone);
             # a child process with all the CPUs this process was allowed before it pinned itself
             if cpus_all:

@@ -11,6 +11,9 @@ What is captured (SURVEY.md section 4 fixture plan):
   traj_<scenario>.npz — seeded trajectories: actions, shuffle order, canonical state, rewards,
                         done, grid.encode(), obs (full for 2 seeds, CRC32 for all), final MT state
   interact.npz   — hand-built pickup / drop / toggle / error scenes
+  live.npz       — the cases of tests/test_oracle_vs_reference.py: seeded runs as digests of every observation,
+                   encoding and state field and of the final MT state (rewards / done in full), occlusion masks, place_obj /
+                   try_place_obj, agent geometry helpers, rotate_grid
 The reference's arrays are data; no reference source text is stored.
 """
 import os
@@ -422,9 +425,102 @@ def gen_interact(m, out):
     np.savez_compressed(out, **d)
 
 
+def gen_live(m, out):
+    """What tests/test_oracle_vs_reference.py checks the oracle against, beyond the trajectory fixtures: the reference
+    stepped on the fresh seeds / actions / scenario knobs of that file's cases (test_oracle_vs_reference.live_cases()),
+    recorded as digests (refstate.digest) of every observation, encoding and canonical state field and of the final
+    MT19937 key, with the actions, rewards and done flags in full; its occlusion masks, place_obj / try_place_obj results,
+    agent geometry helpers and rotate_grid on that file's inputs."""
+    import test_oracle_vs_reference as L
+    from marlgrid.agents import occlude_mask, GridAgentInterface as RefAgent
+    from marlgrid.base import rotate_grid as ref_rot
+    from marlgrid.objects import Wall, Goal
+    dg = refstate.digest
+    d = {}
+    for name, seed, T in L.live_cases():
+        spec = scenarios.registered(name)
+        env = refstate.make_ref_env(spec, scenarios.ref_recipe(name), seed=seed)
+        n = len(spec["agents"])
+        rng = np.random.RandomState(seed)
+
+        def state():
+            c = refstate.canonical(env)
+            return [dg(c[k]) for k in CANON]
+        # head: ctor state | reset state | MT19937 key words at the end | its position | reset obs (one per agent)
+        # steps[t]: obs (one per agent) | encode | state | obs of the reset after a done step (0: no reset)
+        ctor = state()
+        reset_obs = [dg(x) for x in env.reset()]
+        head = ctor + state()
+        actions, rewards, done = np.zeros((T, n), np.int8), np.zeros((T, n), np.float64), np.zeros(T, bool)
+        steps = np.zeros((T, 2 * n + 1 + len(CANON)), np.uint64)
+        for t in range(T):
+            a = rng.randint(0, 7, size=n)
+            o, r, dn, _ = env.step(a)
+            assert len(o) == n
+            actions[t], rewards[t], done[t] = a, np.asarray(r, np.float64), dn
+            seen = [dg(x) for x in o] + [dg(env.grid.encode())] + state()
+            steps[t] = seen + ([dg(x) for x in env.reset()] if dn else [0] * n)
+        st = env.np_random.get_state()
+        head += [dg(np.asarray(st[1], np.uint32)), int(st[2])] + reset_obs
+        p = L.case_key(name, seed, T) + "/"
+        d.update({p + "head": np.array(head, np.uint64), p + "steps": steps, p + "actions": actions, p + "rewards": rewards,
+                  p + "done": done})
+        print("live", name, seed, T, flush=True)
+    rng = np.random.RandomState(123)
+    for vs in L.OCCLUSION_VIEWS:
+        for off in (0, 1):
+            Ms = []
+            for _ in range(150):         # (the test draws the same masks from the same RandomState)
+                Tm = rng.rand(vs, vs) < rng.choice([0.6, 0.8, 0.95])
+                M = np.asarray(occlude_mask(Tm.copy(), (vs // 2, vs - 1 - off)))
+                assert M.shape == Tm.shape and set(np.unique(M).tolist()) <= {0, 1}
+                Ms.append(M)
+            d["occlusion/vs%d_off%d" % (vs, off)] = np.packbits(np.stack(Ms).astype(bool))
+    name = "MarlGrid-3AgentCluttered11x11-v0"
+    spec = scenarios.registered(name)
+    for seed in L.PLACE_SEEDS:
+        env = refstate.make_ref_env(spec, scenarios.ref_recipe(name), seed=seed)
+        env.reset()
+        walls = np.array([tuple(env.place_obj(Wall(), max_tries=100)) for _ in range(6)], np.int64)
+        goal = np.array(tuple(env.place_obj(Goal(color="green", reward=1), top=(2, 3), size=(4, 20), max_tries=100)), np.int64)
+        rng = np.random.RandomState(seed)
+        xy, ok = np.zeros((30, 2), np.int64), np.zeros(30, bool)
+        for i in range(30):
+            x, y = int(rng.randint(0, 11)), int(rng.randint(0, 11))
+            xy[i] = x, y
+            ok[i] = bool(env.try_place_obj(Wall(), np.array([x, y])))
+        c = refstate.canonical(env)
+        st = env.np_random.get_state()
+        p = "place/%d/" % seed
+        d.update({p + "walls": walls, p + "goal": goal, p + "xy": xy, p + "ok": ok,
+                  p + "state": np.array([refstate.digest(c[k]) for k in CANON], np.uint64),
+                  p + "mt": np.array([refstate.digest(np.asarray(st[1], np.uint32)), int(st[2])], np.uint64)})
+    rng = np.random.RandomState(5)
+    for vs, off in L.GEOMETRY_VIEWS:
+        ref = RefAgent(view_size=vs, view_offset=off)
+        N = 200
+        pos = rng.randint(0, 20, size=(N, 2))
+        dr = rng.randint(0, 4, size=N)
+        ij = rng.randint(-3, 24, size=(N, 2))
+        exts, coords, dvec = np.zeros((N, 4), np.int64), np.zeros((N, 2), np.int64), np.zeros((N, 2), np.int64)
+        for b in range(N):
+            ref.pos, ref.dir = tuple(pos[b]), int(dr[b])
+            exts[b] = tuple(ref.get_view_exts())
+            coords[b] = tuple(int(v) for v in ref.get_view_coords(*ij[b]))
+            dvec[b] = ref.dir_vec
+        p = "geometry/vs%d_off%d/" % (vs, off)
+        d.update({p + "pos": pos, p + "dir": dr, p + "ij": ij, p + "exts": exts, p + "coords": coords, p + "dir_vec": dvec})
+    a = np.arange(3 * 5).reshape(3, 5)
+    b = np.arange(2 * 3 * 5).reshape(2, 3, 5)
+    for k in range(-1, 6):
+        d["rotate/a/%d" % k] = np.asarray(ref_rot(a, k))
+        d["rotate/b/%d" % k] = np.stack([ref_rot(b[i], k) for i in range(2)])
+    np.savez_compressed(out, **d)
+
+
 def main():
     m = refload.load()
-    which = sys.argv[1:] or ["atlas", "rng", "occlusion", "traj", "interact", "frames"]
+    which = sys.argv[1:] or ["atlas", "rng", "occlusion", "traj", "interact", "frames", "live"]
     if "atlas" in which:
         gen_atlas(m, os.path.join(HERE, "atlas.npz"))
     if "rng" in which:
@@ -445,6 +541,8 @@ def main():
         gen_frames_big(os.path.join(HERE, "frames_big.npz"))
     if "interact" in which:
         gen_interact(m, os.path.join(HERE, "interact.npz"))
+    if "live" in which:
+        gen_live(m, os.path.join(HERE, "live.npz"))
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print("%-60s %8d B" % (f, os.path.getsize(os.path.join(HERE, f))))

@@ -1,6 +1,7 @@
 """Reference-side helpers (build container only): construct a reference env for a scenario spec
 and dump its state in the id-free canonical form that the oracle and the HIP path are compared in.
 """
+import hashlib
 import zlib
 
 import numpy as np
@@ -222,3 +223,14 @@ class OrderSpy(object):
 
 def crc(a):
     return zlib.crc32(np.ascontiguousarray(a, dtype=np.uint8).tobytes()) & 0xFFFFFFFF
+
+
+def digest(a):
+    """64-bit digest of an integer / bool array: its shape and its values, whatever the dtype (equal digests <=>
+    np.array_equal, up to hash collisions).  How the live-parity fixtures (tests/golden/live.npz) hold what the
+    reference returned."""
+    a = np.asarray(a)
+    h = hashlib.blake2b(digest_size=8)
+    h.update(np.asarray(a.shape, np.int64).tobytes())
+    h.update(np.ascontiguousarray(a, dtype=np.int64).tobytes())
+    return np.uint64(int.from_bytes(h.digest(), "little"))

@@ -27,7 +27,8 @@ def test_bench_two_ranks_on_one_gpu_through_the_drivers_launch_line():
                    or k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"))}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-           "--oversubscribe", "--control-plane", "nccl", "--min-seconds", "1", "--no-strong", "--no-pipeline", "--cpu-seconds", "3"]
+           "--oversubscribe", "--control-plane", "nccl", "--full", "--min-seconds", "1", "--no-strong", "--no-pipeline",
+           "--cpu-seconds", "3"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -80,7 +81,8 @@ def test_bench_eight_ranks_rehearsal_on_one_gpu():
     Bp = 12288                                          # 347 MB of observations per buffer: above the placement threshold
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5",
-           "--oversubscribe", "--batch-per-gpu", str(Bp), "--min-seconds", "0.5", "--no-strong", "--no-pipeline", "--cpu-seconds", "2"]
+           "--oversubscribe", "--batch-per-gpu", str(Bp), "--full", "--min-seconds", "0.5", "--no-strong", "--no-pipeline",
+           "--cpu-seconds", "2"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -105,3 +107,41 @@ def test_bench_eight_ranks_rehearsal_on_one_gpu():
     assert par["ok"] is True and par["ok_by_rank"] == [True] * 8 and par["envs"] == 8 and par["steps"] >= 25
     assert out["cpu_baseline"]["value"] > 0 and out["roofline"]["traffic"] is None
     assert "errors" not in out or set(out["errors"]) <= {"pmc"}, out.get("errors")
+
+
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain line (no --full): exactly --steps timed steps, ms_per_step consistent with value, none of --full's legs; and
+    --dump-outputs writes what the last timed step returned — float32, within 64 MB — identically in two runs."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items()
+           if not (k.startswith("MG_") or k.startswith("MARLGRID_") or k.startswith("BENCH_TEST_")
+                   or k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"))}
+    B, dumps = 4096, []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3",
+               "--batch-per-gpu", str(B), "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 7 and out["warmup"] == 3 and out["full"] is False and out["timing"]["blocks"]["count"] == 1
+        assert out["unit"] == "agent-steps/s" and out["higher_is_better"] is True and out["dtype"] == "u8"
+        assert abs(out["value"] - B * 3 / (out["ms_per_step"] * 1e-3)) <= 1e-6 * out["value"]
+        assert abs(out["timing"]["seconds_timed"] * 1e3 / 7 - out["ms_per_step"]) <= 1e-6 * out["ms_per_step"]
+        for key in ("parity_after_timed", "cpu_baseline", "roofline", "pmc", "extra", "clocks"):
+            assert key not in out, key
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["done.npy", "obs.npy", "obs_env_ids.npy", "rewards.npy"], files
+        arrays = {f[:-4]: np.load(str(d / f)) for f in files}
+        assert sum((d / f).stat().st_size for f in files) <= 64 * 1000 * 1000
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        ids = arrays["obs_env_ids"]
+        assert arrays["rewards"].shape == (B, 3) and arrays["done"].shape == (B,)
+        assert arrays["obs"].shape[0] == len(ids) >= 1 and arrays["obs"].shape[1:] == (3, 56, 56, 3)
+        assert np.array_equal(ids, np.unique(ids)) and ids.min() >= 0 and ids.max() < B
+        assert arrays["obs"].min() >= 0 and arrays["obs"].max() <= 255 and arrays["obs"].max() > 0
+        dumps.append(arrays)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k

@@ -1,142 +1,170 @@
-"""Build-container only (skipped where /root/reference is absent): the oracle stepped side by side
-with the REAL reference (imported through tests/golden/refshim) on fresh seeds / actions that are
-not in the committed fixtures."""
+"""CPU: the oracle against what the REAL reference returned on fresh seeds / actions that are not in the trajectory
+fixtures — every observation, encoding and canonical state field of every step and the final MT19937 state (as digests:
+refstate.digest), rewards and done flags; occlusion, place_obj / try_place_obj, agent geometry helpers and rotate_grid.  The
+reference's side is recorded in tests/golden/live.npz by tests/golden/make_golden.py (`live`), which steps the reference
+through tests/golden/refshim on exactly the cases listed here."""
+import functools
+import os
+
 import numpy as np
 import pytest
 
 import canon
-import refload
 import scenarios
+from golden import refstate  # only for digest(); does not import the reference
 from oracle import oracle as O
 
-pytestmark = pytest.mark.reference
+LIVE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "live.npz")
+
+SIDE_BY_SIDE = [("Test-3AgentCluttered9x9-hetero-views", 9010, 120),
+                ("MarlGrid-3AgentCluttered15x15-v0", 9001, 250),
+                ("Test-4AgentEmpty5x5-crowded-noghost", 9002, 200),
+                ("Goalcycle-demo-solo-v0", 9003, 200),
+                ("Custom-8AgentCluttered30x30", 9004, 60)]
+FUZZ = list(range(40)) + [102, 115, 124, 167, 181, 202, 349, 371, 380, 399, 572]
+FUZZ_WIDE = list(range(28))
+OCCLUSION_VIEWS = (3, 5, 7, 9, 13, 2, 4, 6, 8, 16, 17, 22, 31)
+PLACE_SEEDS = (1, 2, 3, 4)
+GEOMETRY_VIEWS = ((7, 0), (7, 1), (5, 2), (9, 3), (3, 0), (7, 6), (6, 0), (6, 1), (4, 3), (2, 0), (8, 2))
 
 
-@pytest.mark.parametrize("name,seed,T", [("Test-3AgentCluttered9x9-hetero-views", 9010, 120),
-                                          ("MarlGrid-3AgentCluttered15x15-v0", 9001, 250),
-                                          ("Test-4AgentEmpty5x5-crowded-noghost", 9002, 200),
-                                          ("Goalcycle-demo-solo-v0", 9003, 200),
-                                          ("Custom-8AgentCluttered30x30", 9004, 60)])
+def fuzz_args(i):
+    return "Fuzz-%d" % i, 31000 + i, 90
+
+
+def fuzz_wide_args(i):
+    return "FuzzW-%d" % i, 47000 + i, 45
+
+
+def live_cases():
+    """(scenario, seed, steps) of every recorded run"""
+    return SIDE_BY_SIDE + [fuzz_args(i) for i in FUZZ] + [fuzz_wide_args(i) for i in FUZZ_WIDE]
+
+
+def case_key(name, seed, T):
+    return "%s@%d@%d" % (name, seed, T)
+
+
+@functools.lru_cache(maxsize=1)
+def _live():
+    with np.load(LIVE) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _get(prefix):
+    g = _live()
+    p = prefix + "/"
+    out = {k[len(p):]: v for k, v in g.items() if k.startswith(p)}
+    assert out, "no recorded reference run %r in %s" % (prefix, LIVE)
+    return out
+
+
+@pytest.mark.parametrize("name,seed,T", SIDE_BY_SIDE)
 def test_live_side_by_side(name, seed, T):
-    import refstate
+    g = _get(case_key(name, seed, T))
     spec = scenarios.registered(name)
-    env = refstate.make_ref_env(spec, scenarios.ref_recipe(name), seed=seed)
     orc = O.make_env(spec, seed=seed)
     n = len(spec["agents"])
-    rng = np.random.RandomState(seed)
+    S = len(canon.KEYS) - 1
+    # head: ctor state | reset state | MT19937 key words at the end | its position | reset obs (one per agent)
+    # steps[t]: obs (one per agent) | encode | state | obs of the reset after a done step
+    head, steps = g["head"], g["steps"]
+    assert g["actions"].shape == (T, n) and head.shape == (2 * S + 2 + n,) and steps.shape == (T, 2 * n + 1 + S)
 
-    def same_obs(a, b):       # lists of per-agent arrays (shapes differ when agents have their own views)
-        return len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
+    def same_obs(o, want, what):       # lists of per-agent arrays (shapes differ when agents have their own views)
+        assert len(o) == len(want) == n, what
+        assert [refstate.digest(x) for x in o] == list(want), what
 
-    def same_state(what):
-        a, b = refstate.canonical(env), canon.oracle_canonical(orc)
-        for k in canon.KEYS[:-1]:
-            assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), (what, k)
+    def same_state(want, what):
+        c = canon.oracle_canonical(orc)
+        for j, k in enumerate(canon.KEYS[:-1]):
+            assert refstate.digest(c[k]) == want[j], (what, k)
 
-    same_state("ctor")
-    assert same_obs(env.reset(), orc.reset())
-    same_state("reset")
+    same_state(head[:S], "ctor")
+    same_obs(orc.reset(), head[2 * S + 2:], "reset")
+    same_state(head[S:2 * S], "reset")
     for t in range(T):
-        a = rng.randint(0, 7, size=n)
-        o1, r1, d1, _ = env.step(a)
-        o2, r2, d2, _ = orc.step(a)
-        assert same_obs(o1, o2), t
-        assert np.array_equal(r1, r2) and d1 == d2, t
-        assert np.array_equal(env.grid.encode(), orc.encode()), t
-        same_state("step %d" % t)
-        if d1:
-            assert same_obs(env.reset(), orc.reset())
-    st = env.np_random.get_state()
+        o2, r2, d2, _ = orc.step(g["actions"][t].astype(np.int64))
+        same_obs(o2, steps[t, :n], t)
+        assert np.array_equal(g["rewards"][t], r2) and bool(g["done"][t]) == d2, t
+        assert refstate.digest(orc.encode()) == steps[t, n], t
+        same_state(steps[t, n + 1:n + 1 + S], "step %d" % t)
+        if g["done"][t]:
+            same_obs(orc.reset(), steps[t, n + 1 + S:], "reset after step %d" % t)
     mt, pos = orc.mt_state()
-    assert st[2] == pos and np.array_equal(st[1], mt)
+    assert int(head[2 * S + 1]) == pos and refstate.digest(np.asarray(mt, np.uint32)) == head[2 * S]
 
 
-@pytest.mark.parametrize("i", list(range(40)) + [102, 115, 124, 167, 181, 202, 349, 371, 380, 399, 572])
+@pytest.mark.parametrize("i", FUZZ)
 def test_live_fuzz(i):
     """random constructor knobs (scenarios.fuzz_case): reference == oracle, every step"""
-    test_live_side_by_side("Fuzz-%d" % i, 31000 + i, 90)
+    test_live_side_by_side(*fuzz_args(i))
 
 
-@pytest.mark.parametrize("i", list(range(28)))
+@pytest.mark.parametrize("i", FUZZ_WIDE)
 def test_live_fuzz_beyond_the_old_limits(i):
     """scenarios.fuzz_wide_case: up to 32 agents, views up to 31 x 31, grids up to 255 x 255 — reference == oracle, every step"""
-    test_live_side_by_side("FuzzW-%d" % i, 47000 + i, 45)
+    test_live_side_by_side(*fuzz_wide_args(i))
 
 
 def test_occlusion_live_random():
-    m = refload.load()
-    from marlgrid.agents import occlude_mask
     rng = np.random.RandomState(123)
-    for vs in (3, 5, 7, 9, 13, 2, 4, 6, 8, 16, 17, 22, 31):
+    for vs in OCCLUSION_VIEWS:
         for off in (0, 1):
-            for _ in range(150):
+            M = np.unpackbits(_live()["occlusion/vs%d_off%d" % (vs, off)])[:150 * vs * vs].reshape(150, vs, vs).astype(bool)
+            for i in range(150):
                 T = rng.rand(vs, vs) < rng.choice([0.6, 0.8, 0.95])
-                want = occlude_mask(T.copy(), (vs // 2, vs - 1 - off))
-                assert np.array_equal(O.occlude(T, (vs // 2, vs - 1 - off)), want)
+                assert np.array_equal(O.occlude(T, (vs // 2, vs - 1 - off)), M[i]), (vs, off, i)
 
 
 def test_live_place_obj_and_try_place_obj():
     """place_obj / try_place_obj on a live grid (base.py:664-708): positions, success flags and RNG
     consumption of the oracle against the reference's own methods."""
-    import refstate
-    from marlgrid.objects import Wall, Goal
     name = "MarlGrid-3AgentCluttered11x11-v0"
     spec = scenarios.registered(name)
-    for seed in (1, 2, 3, 4):
-        env = refstate.make_ref_env(spec, scenarios.ref_recipe(name), seed=seed)
+    for seed in PLACE_SEEDS:
+        g = _get("place/%d" % seed)
         orc = O.OracleEnv(spec, seed=seed)
-        env.reset(); orc.reset()
+        orc.reset()
         for i in range(6):
-            pos = env.place_obj(Wall(), max_tries=100)
-            assert tuple(pos) == orc.place_obj(1, max_tries=100)
-        pos = env.place_obj(Goal(color="green", reward=1), top=(2, 3), size=(4, 20), max_tries=100)
-        assert tuple(pos) == orc.place_obj(2, region=(2, 3, 6, 11), max_tries=100)
-        rng = np.random.RandomState(seed)
+            assert tuple(g["walls"][i]) == orc.place_obj(1, max_tries=100)
+        assert tuple(g["goal"]) == orc.place_obj(2, region=(2, 3, 6, 11), max_tries=100)
         for i in range(30):
-            x, y = int(rng.randint(0, 11)), int(rng.randint(0, 11))
-            ok = env.try_place_obj(Wall(), np.array([x, y]))
-            assert bool(ok) == orc.try_place_obj(1, x, y), (seed, i, x, y)
-        a, b = refstate.canonical(env), canon.oracle_canonical(orc)
-        for k in canon.KEYS[:-1]:
-            assert np.array_equal(np.asarray(a[k]), np.asarray(b[k])), k
-        st = env.np_random.get_state()
+            x, y = (int(v) for v in g["xy"][i])
+            assert bool(g["ok"][i]) == orc.try_place_obj(1, x, y), (seed, i, x, y)
+        c = canon.oracle_canonical(orc)
+        for j, k in enumerate(canon.KEYS[:-1]):
+            assert refstate.digest(c[k]) == g["state"][j], k
         mt, p = orc.mt_state()
-        assert st[2] == p and np.array_equal(st[1], mt)
+        assert int(g["mt"][1]) == p and refstate.digest(np.asarray(mt, np.uint32)) == g["mt"][0]
 
 
 def test_agent_geometry_helpers_match_the_reference():
     """GridAgentInterface.get_view_exts / get_view_coords / relative_coords / in_view (agents.py:200-285):
     the product's batched tensor versions == the reference's per-agent methods on random poses"""
     import torch
-    refload.load()
-    from marlgrid.agents import GridAgentInterface as RefAgent
     from marlgrid_amd.agents import GridAgentInterface as Agent
-    rng = np.random.RandomState(5)
-    for vs, off in ((7, 0), (7, 1), (5, 2), (9, 3), (3, 0), (7, 6), (6, 0), (6, 1), (4, 3), (2, 0), (8, 2)):
-        ref = RefAgent(view_size=vs, view_offset=off)
-        N = 200
-        pos = rng.randint(0, 20, size=(N, 2))
-        d = rng.randint(0, 4, size=N)
-        ij = rng.randint(-3, 24, size=(N, 2))
+    for vs, off in GEOMETRY_VIEWS:
+        g = _get("geometry/vs%d_off%d" % (vs, off))
+        pos, d, ij = g["pos"], g["dir"], g["ij"]
+        N = len(pos)
         tp, td = torch.from_numpy(pos), torch.from_numpy(d)
         exts = Agent._view_exts(tp, td, vs, off).numpy()
         vx, vy = Agent._view_coords(tp, td, torch.from_numpy(ij[:, 0]), torch.from_numpy(ij[:, 1]), vs, off)
         for b in range(N):
-            ref.pos, ref.dir = tuple(pos[b]), int(d[b])
-            assert tuple(exts[b]) == tuple(ref.get_view_exts())
-            assert (int(vx[b]), int(vy[b])) == tuple(int(v) for v in ref.get_view_coords(*ij[b]))
-            assert np.array_equal(Agent._dir_vec(td[b:b + 1])[0].numpy(), ref.dir_vec)
+            assert tuple(exts[b]) == tuple(g["exts"][b])
+            assert (int(vx[b]), int(vy[b])) == tuple(int(v) for v in g["coords"][b])
+            assert np.array_equal(Agent._dir_vec(td[b:b + 1])[0].numpy(), g["dir_vec"][b])
 
 
 def test_rotate_grid_matches_the_reference():
     """marlgrid_amd.base.rotate_grid (torch, trailing (x, y) dims) == base.py:67-80 (numpy)"""
     import torch
-    refload.load()
-    from marlgrid.base import rotate_grid as ref_rot
     from marlgrid_amd.base import rotate_grid
+    g = _live()
     a = np.arange(3 * 5).reshape(3, 5)
     b = np.arange(2 * 3 * 5).reshape(2, 3, 5)
     for k in range(-1, 6):
-        assert np.array_equal(rotate_grid(torch.from_numpy(a.copy()), k).numpy(), ref_rot(a, k))
+        assert np.array_equal(rotate_grid(torch.from_numpy(a.copy()), k).numpy(), g["rotate/a/%d" % k])
         r = rotate_grid(torch.from_numpy(b.copy()), k).numpy()
-        assert all(np.array_equal(r[i], ref_rot(b[i], k)) for i in range(2))
+        assert all(np.array_equal(r[i], g["rotate/b/%d" % k][i]) for i in range(2))

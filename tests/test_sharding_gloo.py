@@ -198,3 +198,37 @@ def test_bench_refuses_measurement_switches():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--selftest-cpu"], capture_output=True,
                        text=True, timeout=120, env=dict(os.environ, MG_RENDER_VARIANT="4"))
     assert r.returncode == 2 and "MG_RENDER_VARIANT" in r.stderr
+
+
+def test_dump_outputs_writes_a_seeded_float32_sample_within_the_budget(tmp_path):
+    """bench.py --dump-outputs' writer on host tensors: rewards / done whole, the observations of a fixed sample of envs (the
+    same ids every time), every file float32 / float64, the whole within DUMP_BYTES"""
+    import importlib.util
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    bench.DUMP_BYTES = 1 << 20
+    B = 300
+    g = torch.Generator().manual_seed(3)
+    obs = torch.randint(0, 256, (B, 3, 14, 14, 3), generator=g, dtype=torch.uint8)
+    rew = torch.rand((B, 3), generator=g)
+    done = torch.rand(B, generator=g) < 0.1
+    got = []
+    for run in range(2):
+        d = str(tmp_path / ("d%d" % run))
+        files = bench.dump_outputs(d, B, (obs, rew, done, {}))
+        assert files == ["done.npy", "obs.npy", "obs_env_ids.npy", "rewards.npy"]
+        a = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+        assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+        assert sum(x.nbytes for x in a.values()) <= bench.DUMP_BYTES
+        ids = a["obs_env_ids"].astype(np.int64)
+        assert 1 <= len(ids) < B and np.array_equal(ids, np.unique(ids))
+        per_env = 3 * 14 * 14 * 3 * 4 + 8
+        assert len(ids) == (bench.DUMP_BYTES - B * 3 * 4 - B * 4) // per_env          # as many as the budget holds
+        assert np.array_equal(a["obs"], obs.numpy()[ids].astype(np.float32))
+        assert np.array_equal(a["rewards"], rew.numpy()) and np.array_equal(a["done"], done.numpy().astype(np.float32))
+        got.append(a)
+    assert all(np.array_equal(got[0][k], got[1][k]) for k in got[0])

@@ -20,6 +20,8 @@
  *                                       (base.py:418-474, 123-147, 103-106, 275-331;
  *                                        agents.py:233-266, 290-343)
  *   mg_encode       MultiGrid.encode    (base.py:196-214; objects.py:90-99)
+ *   mg_encode_views every agent's gen_obs_grid(agent) -> grid.encode(vis_mask) (base.py:418-451, 196-214)
+ *   mg_step_encode_views  mg_step + mg_encode_views: MultiGridEnv.step with encoded views instead of pixels
  *   mg_put_obj      MultiGridEnv.put_obj (base.py:655-662)
  *   mg_place        MultiGridEnv.place_obj / try_place_obj outside _gen_grid (base.py:664-708)
  *   mg_render_frame MultiGridEnv.render's whole-grid image: MultiGrid.render(top_agent=None) +
@@ -268,6 +270,19 @@ int32_t mg_step_render_encode(const MgConfig* cfg, const MgState* st, const void
  * view_agent uint8 [B][n][vs][vs] (shown agent index or 0xFF), vis_mask uint8 [B][n][vs][vs]. */
 int32_t mg_render_obs(const MgConfig* cfg, const MgState* st, uint8_t* obs, uint8_t* view_cells,
                       uint8_t* view_agent, uint8_t* vis_mask, void* stream);
+
+/* MultiGridEnv.step like mg_step_render, but instead of pixels it writes every agent's
+ * gen_obs_grid(agent) -> grid.encode(vis_mask) (base.py:418-451, 196-214) of the stepped state (mg_step, then
+ * mg_encode_views, on `stream`).  views: device uint8 [B][n][vs][vs][3], index [i][j] as encode returns it, any alignment.
+ * Per view cell the (type, colour, state) triple of what `grid.get` returns after hide_item_types — an agent standing on an
+ * object is not encoded, the bottom agent of a stack on an empty cell is —; invisible cells, empty cells, cells outside the
+ * grid and every cell of an inactive agent's view are (0, 0, 0).  n_view must be 0 (view groups: mg_step, then
+ * mg_encode_views per group). */
+int32_t mg_step_encode_views(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes,
+                             float* rewards, const MgGenProgram* auto_reset, uint8_t* views, void* stream);
+/* The same views of the current state (after mg_reset / mg_step), for one view group's cfg: views [B][nv][vs][vs][3] with
+ * nv = n_view, or n_agents when n_view == 0.  Tile size and atlas play no part. */
+int32_t mg_encode_views(const MgConfig* cfg, const MgState* st, uint8_t* views, void* stream);
 
 /* out: device uint8 [B][W][H][3]; vis_mask: device uint8 [B][W][H] or NULL. */
 int32_t mg_encode(const MgConfig* cfg, const MgState* st, const uint8_t* vis_mask, uint8_t* out,

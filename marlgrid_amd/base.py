@@ -416,7 +416,7 @@ class MultiGridEnv(object):
     def __init__(self, agents=[], grid_size=None, width=None, height=None, max_steps=100,
                  reward_decay=True, seed=1337, respawn=False, ghost_mode=True, agent_spawn_kwargs={},
                  batch_size=1, device=None, seeds=None, auto_reset=False, strict=True, obs_buffers=2,
-                 fused_step=True, place_obs=True, encode_in_step=False, _dry=False):
+                 fused_step=True, place_obs=True, encode_in_step=False, obs_format="image", _dry=False):
         if grid_size is not None:
             assert width is None and height is None
             width, height = grid_size, grid_size
@@ -444,6 +444,13 @@ class MultiGridEnv(object):
         # +2.4 % bytes instead of a second launch), by an mg_encode launch behind it otherwise
         self.encode_in_step = bool(encode_in_step)
         self.grid_encoding = None
+        # obs_format="encoded": reset() / step() / gen_obs() return every agent's gen_obs_grid(agent) -> grid.encode(vis_mask)
+        # (base.py:418-451, 196-214) — (B, n, V, V, 3) uint8, index [i, j] — instead of the (B, n, P, P, 3) pixels; the step's
+        # launch writes them (mg_step_encode_views) and nothing is rasterised
+        if obs_format not in ("image", "encoded"):
+            raise ValueError("obs_format must be 'image' or 'encoded' (got %r)" % (obs_format,))
+        self.obs_format = obs_format
+        self._encoded = obs_format == "encoded"
         self._enc_fused = True                 # until the library says MG_E_UNSUPPORTED for this configuration
         # where the observation buffers live: "search" (= True) picks the fastest of a bounded set of candidate
         # allocations by timing the raster itself into each (_place_obs_buffers -> mg_obs_place: <= 2 s, candidates <=
@@ -503,7 +510,8 @@ class MultiGridEnv(object):
         self.seed(seed=seed)
         self.reset()
         self.obs_placement = []
-        if not self._dry and self.place_obs in ("search", "thorough"):
+        # (encoded views are a few MB: plain allocations, nothing to place)
+        if not self._dry and not self._encoded and self.place_obs in ("search", "thorough"):
             self._place_obs_buffers(**self._place_kw)
         self._spec_ctor = self._spec_last     # the constructor-time `_gen_grid` (base.py:369)
         self._retrace = True
@@ -558,7 +566,9 @@ class MultiGridEnv(object):
                 raise ValueError("view_offset out of range")
             key = (a.view_size, a.view_tile_size, a.view_offset, bool(a.see_through_walls))
             for g in self._groups:
-                if g.key == key:
+                # (encoded views: the tile size plays no part — a group's tile size is its first member's, used only by the
+                # pixel views gen_obs_grid() and render() draw on demand)
+                if g.key == key or (self._encoded and g.key[0] == key[0] and g.key[2:] == key[2:]):
                     g.members.append(k)
                     break
             else:
@@ -569,6 +579,13 @@ class MultiGridEnv(object):
         # the first group's view parameters double as "the env's" (what uniform envs have always exposed)
         self.view_size, self.tile_size, self.view_offset, self.see_through_walls = self._groups[0].key
         self.obs_pixels = self.view_size * self.tile_size
+        if self._encoded:       # each agent's observation_space (and a rich agent's 'pov'): Box(0, 255, (V, V, 3), uint8)
+            for a in self.agents:
+                box = spaces.Box(low=0, high=255, shape=(a.view_size, a.view_size, 3), dtype="uint8")
+                if a.observation_style == "image":
+                    a.observation_space = box
+                else:
+                    a.observation_space = spaces.Dict(dict(a.observation_space.spaces, pov=box))
 
     @property
     def num_agents(self):
@@ -609,6 +626,9 @@ class MultiGridEnv(object):
             # `save_step(obs, act, next_obs, rew, done)` sees two different observations.
             for g in self._groups:
                 g.shape = (B, len(g.members), g.pixels, g.pixels, 3)
+                if self._encoded:       # the encoded views; pixels only on demand (_pixel_views)
+                    g.shape = (B, len(g.members), g.view_size, g.view_size, 3)
+                g.pix = None
                 g.ring = [torch.zeros(g.shape, dtype=torch.uint8, device=dev) for _ in range(self.obs_buffers)]
                 g.obs = g.ring[0]
             self._ring = [dict(obs=self._groups[0].ring[i],
@@ -1101,7 +1121,8 @@ class MultiGridEnv(object):
             # the obs kernel keeps 4 waves of per-env scratch (and the atlas, when it fits) in one workgroup's
             # LDS: ask the library, which owns that layout, before anything is uploaded
             need = N.lib().mg_render_obs_lds_bytes(C.byref(cfg))
-            if need < 0 or need > 160 * 1024:
+            raster_fits = 0 <= need <= 160 * 1024
+            if not raster_fits and not self._encoded:      # (encoded views have no per-env pixel scratch)
                 raise NotImplementedError(
                     "this configuration needs %d KiB of LDS per workgroup for 4 waves of per-env scratch; the obs "
                     "kernel has 160 KiB — with 'prestige' agents reduce their number or the tile size (every one of them has "
@@ -1112,7 +1133,7 @@ class MultiGridEnv(object):
             # it per workgroup was 5 us of human_player's 130 us launch (20 instructions per dword, 45 dwords per thread), 1 - 1.6 %
             # of the others'
             cfg.atlas_gather_off = 0
-            name0 = N.render_kernel_name(cfg)[0]
+            name0 = N.render_kernel_name(cfg)[0] if raster_fits else ""
             if name0.endswith(", 2>") and not os.environ.get("MG_NO_GATHER_ATLAS"):
                 ts, seg = g.tile_size, 3 * g.tile_size
                 rs = (16 + seg + 3) // 4 * 4
@@ -1132,8 +1153,11 @@ class MultiGridEnv(object):
             g.cfg = cfg
             # which instantiation of the observation kernel the launcher picks for this group (what rocprofv3 will call the
             # launch) — and a warning, once per configuration, when it is the fully generic one
-            g.kernel_name, generic = N.render_kernel_name(cfg)
-            _warn_generic_kernel(g, generic, bool(cfg.prestige_mask))
+            if self._encoded:
+                g.kernel_name = "mg::encode_views_kernel<%d>" % (g.view_size if g.view_size in (5, 7, 9) else 0)
+            else:
+                g.kernel_name, generic = N.render_kernel_name(cfg)
+                _warn_generic_kernel(g, generic, bool(cfg.prestige_mask))
         g0 = self._groups[0]
         self._cfg, self.atlas, self._obj_dev, self._atlas_dev = g0.cfg, g0.atlas, g0.obj_dev, g0.atlas_dev
         self._tables_version = self.obj_reg.version
@@ -1254,7 +1278,22 @@ class MultiGridEnv(object):
             probe(0)
         # obs / rewards / done are views of the current buffer set (see `obs_buffers`)
         done = self.done_b
-        if self.fused_step and not self._hetero:
+        if self._encoded:
+            if self.fused_step and not self._hetero:
+                # the step and every agent's encoded view, one call (mg_step_encode_views)
+                N.check(self._lib.mg_step_encode_views(C.byref(self._cfg), C.byref(self._state), actions.data_ptr(),
+                                                       actions.element_size(), self.rewards.data_ptr(), prog,
+                                                       self.obs.data_ptr(), stream))
+            else:
+                N.check(self._lib.mg_step(C.byref(self._cfg), C.byref(self._state), actions.data_ptr(),
+                                          actions.element_size(), self.rewards.data_ptr(), prog, stream))
+                if probe is not None:
+                    probe(1)
+                for g in self._groups:       # one launch per view group
+                    N.check(self._lib.mg_encode_views(C.byref(g.cfg), C.byref(self._state), g.obs.data_ptr(), stream))
+            if self.encode_in_step:
+                self._encode_into(self._encoding_buffer())
+        elif self.fused_step and not self._hetero:
             # the whole step — action loop, reset of finished episodes, observation raster — is ONE launch:
             # the wave that renders an env steps it first
             enc_rc = N.E_UNSUPPORTED
@@ -1297,13 +1336,36 @@ class MultiGridEnv(object):
             cells = torch.zeros((B, nv, vs, vs), dtype=torch.uint8, device=self.device)
             shown = torch.zeros_like(cells)
             vis = torch.zeros_like(cells)
-            N.check(self._lib.mg_render_obs(C.byref(g.cfg), C.byref(self._state), g.obs.data_ptr(),
+            N.check(self._lib.mg_render_obs(C.byref(g.cfg), C.byref(self._state), self._pixel_buffer(g).data_ptr(),
                                             cells.data_ptr(), shown.data_ptr(), vis.data_ptr(), self._stream()))
             return cells, shown, vis
+        if self._encoded:
+            for g in self._groups:
+                N.check(self._lib.mg_encode_views(C.byref(g.cfg), C.byref(self._state), g.obs.data_ptr(), self._stream()))
+            return None
         for g in self._groups:
             N.check(self._lib.mg_render_obs(C.byref(g.cfg), C.byref(self._state), g.obs.data_ptr(), None, None,
                                             None, self._stream()))
         return None
+
+    def _pixel_buffer(self, g):
+        """the group's pixel observations: its obs buffer, or — encoded views — a scratch tensor made on first use"""
+        if not self._encoded:
+            return g.obs
+        if g.pix is None:
+            import torch
+            g.pix = torch.zeros((self.batch_size, len(g.members), g.pixels, g.pixels, 3), dtype=torch.uint8, device=self.device)
+        return g.pix
+
+    def _pixel_views(self):
+        """rasterise every group's pixel views of the current state (render()'s side columns) -> {group: tensor}"""
+        if not self._encoded:
+            self._render()
+            return {id(g): g.obs for g in self._groups}
+        for g in self._groups:
+            N.check(self._lib.mg_render_obs(C.byref(g.cfg), C.byref(self._state), self._pixel_buffer(g).data_ptr(), None, None,
+                                            None, self._stream()))
+        return {id(g): g.pix for g in self._groups}
 
     @_on_device
     def gen_obs(self):
@@ -1648,7 +1710,7 @@ class MultiGridEnv(object):
             # here; kept as written — images are square in every shipped scenario.)
             tpw = int(Hp * agent_col_width_frac - 2 * agent_col_padding_px)
             tph = (Wp - 2 * agent_col_padding_px) // max_agents_per_col
-            self._render()
+            pix = self._pixel_views()
             cols = []
             for c0 in range(0, self.num_agents, max_agents_per_col):
                 col = torch.full((K, Hp, tpw + 2 * agent_col_padding_px, 3), pad_grey, dtype=torch.uint8,
@@ -1657,7 +1719,7 @@ class MultiGridEnv(object):
                     g, slot = self._view_slot(k)                            # each view at its own integer zoom
                     P = g.pixels
                     f = int(min(tpw / P, tph / P))
-                    view = g.obs[ids.long(), slot]                          # (K, P, P, 3)
+                    view = pix[id(g)][ids.long(), slot]                     # (K, P, P, 3)
                     view = view.repeat_interleave(f, dim=1).repeat_interleave(f, dim=2) if f > 0 else view[:, :0, :0]
                     vh = vw = P * f
                     o0 = (tph - vw) // 2 + agent_col_padding_px + j * tph

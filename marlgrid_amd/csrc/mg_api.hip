@@ -182,6 +182,24 @@ int32_t mg_encode(const MgConfig* cfg, const MgState* st, const uint8_t* vis_mas
     return rc(mg::launch_encode(*cfg, *st, vis_mask, out, (hipStream_t)stream));
 }
 
+int32_t mg_encode_views(const MgConfig* cfg, const MgState* st, uint8_t* views, void* stream) {
+    int e = check_both(cfg, st);
+    if (e) return e;
+    if (!views) return MG_E_ARG;
+    return rc(mg::launch_encode_views(*cfg, *st, views, (hipStream_t)stream));
+}
+
+int32_t mg_step_encode_views(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
+                             const MgGenProgram* auto_reset, uint8_t* views, void* stream) {
+    int e = check_both(cfg, st);
+    if (e) return e;
+    if (!actions || !rewards || !views) return MG_E_ARG;
+    if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return MG_E_ARG;
+    if (cfg->n_view != 0) return MG_E_ARG;   // as mg_step_render: view groups take mg_step + mg_encode_views per group
+    if (auto_reset && (e = check_prog(cfg, auto_reset))) return e;
+    return rc(mg::launch_step_encode_views(*cfg, *st, actions, action_bytes, rewards, auto_reset, views, (hipStream_t)stream));
+}
+
 int32_t mg_put_obj(const MgConfig* cfg, const MgState* st, int32_t obj, int32_t x, int32_t y,
                    const uint8_t* env_mask, void* stream) {
     int e = check_cfg(cfg);

@@ -22,6 +22,12 @@ int render_min_lds_bytes(const MgConfig& cfg);
 bool render_can_encode(const MgConfig& cfg);      // mg_step_render_encode: this configuration's step launch can write the encoding too
 hipError_t launch_encode(const MgConfig& cfg, const MgState& st, const uint8_t* vis_mask, uint8_t* out,
                          hipStream_t s);
+// every agent's gen_obs_grid -> encode (mg_encode_views.hip): out uint8 [B][nv][vs][vs][3]
+struct EncViewsStep;
+hipError_t launch_encode_views(const MgConfig& cfg, const MgState& st, uint8_t* out, hipStream_t s, const EncViewsStep* fs = nullptr);
+// mg_step_encode_views: the step and the views in one launch where a workgroup of whole envs fits, else the two launches
+hipError_t launch_step_encode_views(const MgConfig& cfg, const MgState& st, const void* actions, int action_bytes,
+                                    float* rewards, const MgGenProgram* prog, uint8_t* out, hipStream_t s);
 hipError_t launch_put_obj(const MgConfig& cfg, const MgState& st, int obj, int x, int y, const uint8_t* mask,
                           hipStream_t s);
 hipError_t launch_place(const MgConfig& cfg, const MgState& st, int what, int x0, int y0, int x1, int y1, int max_tries,

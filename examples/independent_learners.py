@@ -43,6 +43,25 @@ for i_episode in range(2):
             obs_array = next_obs_array
             episode_over = bool(done.all())
 
+# Many episodes without a reset() in between — auto_reset="next_step": the step that ends an env's episode returns its TERMINAL
+# observation with done=True (what a value bootstrap on a time-limit ending looks at: info["truncated"]), the env's next
+# step() is its reset — the new episode's first observation, reward 0, the action row ignored — and NOT a transition:
+# info["reset"] masks it out.  info["episode_return"] / ["episode_length"] where done are the finished episode's.
+env = ClutteredMultiGrid(agents, grid_size=15, n_clutter=10, batch_size=1024, max_steps=50, auto_reset="next_step", episode_info=True)
+obs_array = env.reset()
+with agents.episode():
+    finished, truncated, returns = 0, 0, 0.0
+    for t in range(160):
+        action_array = agents.action_step(obs_array)
+        next_obs_array, reward_array, done, info = env.step(action_array)
+        agents.save_step(obs_array, action_array, next_obs_array, reward_array, done, valid=~info["reset"])
+        finished += int(done.sum())                      # (host syncs: fine for an example)
+        truncated += int(info["truncated"].sum())
+        returns += float(info["episode_return"][done].sum())
+        obs_array = next_obs_array
+    print("  %d episodes finished, %d of them by the time limit alone; mean return per agent %.3f"
+          % (finished, truncated, returns / max(1, 3 * finished)))
+
 # The same loop as a double-buffered sampler: the batch as TWO envs on two streams (MultiGridEnv.pipelined /
 # make(id, pipeline=2) -> marlgrid_amd.sharding.ShardPipeline), stepped in turn.  While part 1's step kernel runs,
 # part 0's policy and step are already queued on the other stream: the launches overlap (+10 % agent-steps/s at

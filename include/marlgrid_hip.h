@@ -22,6 +22,9 @@
  *   mg_encode       MultiGrid.encode    (base.py:196-214; objects.py:90-99)
  *   mg_encode_views every agent's gen_obs_grid(agent) -> grid.encode(vis_mask) (base.py:418-451, 196-214)
  *   mg_step_encode_views  mg_step + mg_encode_views: MultiGridEnv.step with encoded views instead of pixels
+ *   mg_step_ep / mg_step_render_ep / mg_step_encode_views_ep   the three steps above with an MgEpisode: next-step auto-reset
+ *                   (the terminal state is returned, the env's next call is its reset) and the episode's flags, length and
+ *                   return from the step's own launch (base.py:512, 576-581, 627-649)
  *   mg_put_obj      MultiGridEnv.put_obj (base.py:655-662)
  *   mg_place        MultiGridEnv.place_obj / try_place_obj outside _gen_grid (base.py:664-708)
  *   mg_render_frame MultiGridEnv.render's whole-grid image: MultiGrid.render(top_agent=None) +
@@ -280,6 +283,51 @@ int32_t mg_render_obs(const MgConfig* cfg, const MgState* st, uint8_t* obs, uint
  * mg_encode_views per group). */
 int32_t mg_step_encode_views(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes,
                              float* rewards, const MgGenProgram* auto_reset, uint8_t* views, void* stream);
+/* ---- episode boundaries under auto-reset ---------------------------------------------------------------------------
+ *
+ * What a learner needs at the end of an episode and cannot get from outside the launch once the reset is fused into
+ * the step: the observation of the terminal state, WHY the episode ended, and its return and length.  MgEpisode is the
+ * extra argument of the mg_*_ep entry points below (each its twin plus `ep`; ep == NULL: exactly the twin).  All pointers
+ * are caller-owned device memory; NULL = that output is not wanted.  Not part of mg_struct_sizes: mg_episode_struct_size.
+ *
+ * reset_mode 0, SAME-STEP: the twin's behaviour — with a reset program an env whose episode ends is reset inside the
+ * launch; the outputs below are written BEFORE that reset (which also zeroes the env's accumulators).
+ * reset_mode 1, NEXT-STEP (needs the reset program): the step that ends an episode does NOT reset — done[b] = 1 and the
+ * state (and whatever the launch renders or encodes from it) is the terminal one.  The env's NEXT step call is its reset:
+ * "ended" is read off the persistent state — step_count[b] >= max_steps (base.py:649), or every agent record carries
+ * MG_AF_DONE (base.py:627-649; with `respawn` none keeps it) —, the env's action row is ignored altogether (no
+ * MG_ERR_VALUE for an unknown action), nothing spawns late, nothing is shuffled (no RNG draw), every reward is 0, and the
+ * env is reset exactly as mg_reset would (same draws): step_count[b] = 0, done[b] = 0, accumulators 0, out_return 0,
+ * out_length 0, out_flags MG_EPF_RESET.
+ * mg_reset knows nothing of the accumulators: a caller that resets envs by hand zeroes their ep_return rows. */
+#define MG_EPF_TERMINATED 1 /* done, and every agent is done (the `all(agent.done)` half of base.py:649) */
+#define MG_EPF_TRUNCATED 2  /* done and not terminated: step_count >= max_steps alone (base.py:649) */
+#define MG_EPF_RESET 4      /* this call was the env's reset (next-step mode) */
+typedef struct MgEpisode {
+    int32_t reset_mode;     /* 0 same-step, 1 next-step */
+    int32_t reserved0;
+    double* ep_return;      /* [B][n_agents] persistent: the running episode's sum of the step rewards (the float32 values the
+                             * step writes — base.py:576-581 —, added in float64, one add per step) */
+    double* out_return;     /* [B][n_agents] per step: that sum including this step's reward, before any reset — where done[b],
+                             * the finished episode's return.  Needs ep_return. */
+    int32_t* out_length;    /* [B] per step: step_count (base.py:512) after this step, before any reset */
+    uint8_t* out_flags;     /* [B] per step: MG_EPF_* */
+} MgEpisode;
+int32_t mg_episode_struct_size(void);   /* sizeof(MgEpisode) as this build sees it */
+/* MG_E_ARG (no device access): reset_mode outside {0, 1}; reset_mode 1 without a reset program; out_return without ep_return. */
+int32_t mg_step_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
+                   const MgGenProgram* auto_reset, const MgEpisode* ep, void* stream);
+/* mg_step_render with `ep`.  Compiled into instantiations of the step kernel of their own (the plain ones run at their
+ * register limit), for the shapes mg_step_render_encode has: views 7, 9 and those above 9 with 8-pixel tiles, view 7 with
+ * 5-pixel tiles.  MG_E_UNSUPPORTED — nothing launched, call mg_step_ep and mg_render_obs — for every other shape, with
+ * 'prestige' agents, or when the grid or the atlas does not fit LDS.  There is no _ep twin of mg_step_render_encode:
+ * mg_step_render_ep, then mg_encode. */
+int32_t mg_step_render_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
+                          const MgGenProgram* auto_reset, uint8_t* obs, const MgEpisode* ep, void* stream);
+int32_t mg_step_encode_views_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes,
+                                float* rewards, const MgGenProgram* auto_reset, uint8_t* views, const MgEpisode* ep,
+                                void* stream);
+
 /* The same views of the current state (after mg_reset / mg_step), for one view group's cfg: views [B][nv][vs][vs][3] with
  * nv = n_view, or n_agents when n_view == 0.  Tile size and atlas play no part. */
 int32_t mg_encode_views(const MgConfig* cfg, const MgState* st, uint8_t* views, void* stream);

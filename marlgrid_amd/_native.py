@@ -67,6 +67,15 @@ class GenProgram(C.Structure):
                 ("reject", C.c_void_p), ("n_reject", C.c_int32)]
 
 
+class Episode(C.Structure):
+    """MgEpisode: the extra argument of the mg_*_ep calls (episode boundaries under auto-reset); device pointers or None"""
+    _fields_ = [("reset_mode", C.c_int32), ("reserved0", C.c_int32), ("ep_return", C.c_void_p), ("out_return", C.c_void_p),
+                ("out_length", C.c_void_p), ("out_flags", C.c_void_p)]
+
+
+EPF_TERMINATED, EPF_TRUNCATED, EPF_RESET = 1, 2, 4
+RESET_SAME_STEP, RESET_NEXT_STEP = 0, 1
+
 PLACE_MAX, PLACE_ALL = 8, 136
 PLACE_STIR, PLACE_THOROUGH, PLACE_NO_REUSE = 1, 2, 4
 PLACE_STOP = {0: "", 1: "found", 2: "cap", 3: "time", 4: "memory", 5: "out of memory", 6: "small", 7: "not HBM-bound"}
@@ -97,7 +106,8 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "lib
 SYMBOLS = ["mg_abi_version", "mg_struct_sizes", "mg_host_flag_alloc", "mg_host_flag_free", "mg_obs_alloc", "mg_obs_free", "mg_obs_place", "mg_obs_release", "mg_obs_trim", "mg_build_info", "mg_error_string", "mg_mt_seed", "mg_reset", "mg_step", "mg_step_render", "mg_step_render_encode",
            "mg_render_obs",
            "mg_encode", "mg_put_obj", "mg_place", "mg_render_frame", "mg_time_render_obs",
-           "mg_render_obs_lds_bytes", "mg_render_kernel_name", "mg_step_encode_views", "mg_encode_views"]
+           "mg_render_obs_lds_bytes", "mg_render_kernel_name", "mg_step_encode_views", "mg_encode_views",
+           "mg_episode_struct_size", "mg_step_ep", "mg_step_render_ep", "mg_step_encode_views_ep"]
 
 _lib = None
 _path = LIB_PATH
@@ -168,6 +178,16 @@ def lib():
     L.mg_step_render_encode.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp, vp]
     L.mg_step_encode_views.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp]
     L.mg_encode_views.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp]
+    L.mg_episode_struct_size.argtypes = []
+    L.mg_episode_struct_size.restype = i32
+    if L.mg_episode_struct_size() != C.sizeof(Episode):
+        raise ImportError("marlgrid_amd: MgEpisode is %d bytes in %s, %d in marlgrid_amd/_native.py"
+                          % (L.mg_episode_struct_size(), path, C.sizeof(Episode)))
+    L.mg_step_ep.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), C.POINTER(Episode), vp]
+    L.mg_step_render_ep.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp,
+                                    C.POINTER(Episode), vp]
+    L.mg_step_encode_views_ep.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp,
+                                          C.POINTER(Episode), vp]
     L.mg_render_obs.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp, vp, vp, vp]
     L.mg_encode.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp, vp]
     L.mg_put_obj.argtypes = [C.POINTER(Config), C.POINTER(State), i32, i32, i32, vp, vp]

@@ -254,7 +254,15 @@ class IndependentLearners(object):
         dev = obs_array.device if torch.is_tensor(obs_array) else acts[0].device
         return torch.stack([a.to(dev).reshape(-1).long() for a in acts], dim=1)
 
-    def save_step(self, obs, act, next_obs, rew, done):
+    def save_step(self, obs, act, next_obs, rew, done, valid=None):
+        """valid: (B,) bool or None — the rows that ARE transitions.  With auto_reset="next_step" the step() that resets an
+        env hands back the new episode's first observation for it, reward 0, its action row ignored (info["reset"]): that row
+        is no transition — `save_step(obs, act, next_obs, rew, done, valid=~info["reset"])` leaves it out (one host sync: the
+        number of rows kept)."""
+        if valid is not None:
+            import torch
+            keep = torch.nonzero(valid).squeeze(1)
+            obs, act, next_obs, rew, done = (x.index_select(0, keep) for x in (obs, act, next_obs, rew, done))
         for k, agent in enumerate(self.agents):
             agent.save_step(obs[:, k], act[:, k], next_obs[:, k], rew[:, k], done)
 

@@ -416,7 +416,8 @@ class MultiGridEnv(object):
     def __init__(self, agents=[], grid_size=None, width=None, height=None, max_steps=100,
                  reward_decay=True, seed=1337, respawn=False, ghost_mode=True, agent_spawn_kwargs={},
                  batch_size=1, device=None, seeds=None, auto_reset=False, strict=True, obs_buffers=2,
-                 fused_step=True, place_obs=True, encode_in_step=False, obs_format="image", _dry=False):
+                 fused_step=True, place_obs=True, encode_in_step=False, obs_format="image", episode_info=False,
+                 _dry=False):
         if grid_size is not None:
             assert width is None and height is None
             width, height = grid_size, grid_size
@@ -428,7 +429,25 @@ class MultiGridEnv(object):
         self.agent_spawn_kwargs = agent_spawn_kwargs
         self.ghost_mode = ghost_mode
         self.batch_size = int(batch_size)
+        # auto_reset: False; True = "same_step" — an env whose episode ends is reset inside the same launch, `done` reports the
+        # end and the observation returned is already the next episode's first —; "next_step" (what EnvPool and Gymnasium >= 1.0
+        # do): the step that ends an episode returns the TERMINAL state's observation with done=True and does not reset; the
+        # env's next step() ignores that env's action row and is its reset — the new episode's first observation, reward 0,
+        # done=False.  One launch per step either way (mg_*_ep).
+        if auto_reset is True or auto_reset is False or auto_reset is None:
+            auto_reset = bool(auto_reset)
+        if auto_reset not in (False, True, "same_step", "next_step"):
+            raise ValueError("auto_reset must be False, True (= 'same_step'), 'same_step' or 'next_step' (got %r)" % (auto_reset,))
         self.auto_reset = bool(auto_reset)
+        self.auto_reset_mode = None if not auto_reset else "next_step" if auto_reset == "next_step" else "same_step"
+        # episode_info=True: step()'s fourth value is {"terminated", "truncated", "reset": (B,) bool, "episode_return": (B, n)
+        # float64, "episode_length": (B,) int32} — device tensors of the step's buffer set, like rewards and done — written by
+        # the step's own launch: terminated = done and every agent is done, truncated = done by the time limit alone
+        # (base.py:649), return / length of the running episode BEFORE any reset (where done: of the finished episode),
+        # reset = this call was the env's reset ("next_step" only).  False: {} — and unless auto_reset="next_step" the plain
+        # entry points are called, exactly as before.
+        self.episode_info = bool(episode_info)
+        self._use_ep = self.episode_info or self.auto_reset_mode == "next_step"
         # Per-env runtime errors (the reference's exceptions).  strict=True: raised without giving up the
         # asynchronous launch queue — the kernels raise a one-word flag in host-mapped memory that every
         # step()/reset() polls (no stream synchronize), so the exception surfaces at the next call into the env
@@ -441,7 +460,8 @@ class MultiGridEnv(object):
         self.fused_step = bool(fused_step)     # step() = one launch (mg_step_render) instead of mg_step + mg_render_obs
         # encode_in_step=True: every step() (and reset()) also leaves `grid.encode()` of the batch — (B, W, H, 3) uint8,
         # base.py:196-214 — in `self.grid_encoding`, written by the step's own launch where it can (mg_step_render_encode:
-        # +2.4 % bytes instead of a second launch), by an mg_encode launch behind it otherwise
+        # +2.4 % bytes instead of a second launch), by an mg_encode launch behind it otherwise — also with episode_info /
+        # auto_reset="next_step": mg_step_render_encode has no _ep twin, the step is mg_step_render_ep and mg_encode follows
         self.encode_in_step = bool(encode_in_step)
         self.grid_encoding = None
         # obs_format="encoded": reset() / step() / gen_obs() return every agent's gen_obs_grid(agent) -> grid.encode(vis_mask)
@@ -452,6 +472,7 @@ class MultiGridEnv(object):
         self.obs_format = obs_format
         self._encoded = obs_format == "encoded"
         self._enc_fused = True                 # until the library says MG_E_UNSUPPORTED for this configuration
+        self._ep_fused = True                  # the same for mg_step_render_ep
         # where the observation buffers live: "search" (= True) picks the fastest of a bounded set of candidate
         # allocations by timing the raster itself into each (_place_obs_buffers -> mg_obs_place: <= 2 s, candidates <=
         # min(a quarter of the free memory, 32 GiB)); "thorough": the long search (a second pass, larger candidates, one
@@ -638,6 +659,27 @@ class MultiGridEnv(object):
             self._ring_i = 0
             self.obs, self.rewards, self.done_t = (self._ring[0][k] for k in ("obs", "rewards", "done"))
             self.done_b = self.done_t.view(torch.bool)      # the same bytes, as the bool tensor step() returns
+            # episode boundaries (mg_*_ep): the persistent return accumulator; per buffer set the step's outputs and, made
+            # from its flag byte by ONE small elementwise launch, the three bool tensors of the info dict (the three flags
+            # exclude each other — truncated is "done and not terminated", a reset call is not done —: flag == 1 / 2 / 4)
+            self.ep_return_t = None
+            if self.episode_info:
+                self.ep_return_t = torch.zeros((B, n), dtype=torch.float64, device=dev)
+                self._ep_vals = torch.tensor([[N.EPF_TERMINATED], [N.EPF_TRUNCATED], [N.EPF_RESET]], dtype=torch.uint8, device=dev)
+                for r in self._ring:
+                    r["ep_return"] = torch.zeros((B, n), dtype=torch.float64, device=dev)
+                    r["ep_length"] = torch.zeros((B,), dtype=torch.int32, device=dev)
+                    r["ep_flags"] = torch.zeros((B,), dtype=torch.uint8, device=dev)
+                    r["ep_bits"] = bits = torch.zeros((3, B), dtype=torch.bool, device=dev)
+                    r["info"] = {"terminated": bits[0], "truncated": bits[1], "reset": bits[2], "episode_return": r["ep_return"],
+                                 "episode_length": r["ep_length"]}
+            if self._use_ep:
+                for r in self._ring:
+                    r["ep"] = N.Episode(N.RESET_NEXT_STEP if self.auto_reset_mode == "next_step" else N.RESET_SAME_STEP, 0,
+                                        self.ep_return_t.data_ptr() if self.episode_info else None,
+                                        r["ep_return"].data_ptr() if self.episode_info else None,
+                                        r["ep_length"].data_ptr() if self.episode_info else None,
+                                        r["ep_flags"].data_ptr() if self.episode_info else None)
             # one word of pinned host memory the kernels raise when they record an error in error_t: polled by
             # step()/reset() instead of a nonzero() + .item() round trip through the stream (mapped while the
             # env's device is current: the device pointer is this device's view of the word)
@@ -1220,11 +1262,17 @@ class MultiGridEnv(object):
         if self._dry:
             self._dry_trace = (template, ops)     # host-only instance: the recorded layout, nothing runs
             return None
+        import torch
         self._sync_tables()
         prog = self._program(template, ops)
         self._reset_prog, self._retrace = prog, False
         N.check(self._lib.mg_reset(C.byref(self._cfg), C.byref(self._state), C.byref(prog),
                                    self._mask_ptr(env_mask), self._stream()))
+        if self.ep_return_t is not None:       # (mg_reset knows nothing of the episode accumulators)
+            if env_mask is None:
+                self.ep_return_t.zero_()
+            else:
+                self.ep_return_t.masked_fill_((self._mask_keep != 0).unsqueeze(1), 0.0)
         self._render()
         if self.encode_in_step:
             self._encode_into(self._encoding_buffer())
@@ -1278,7 +1326,9 @@ class MultiGridEnv(object):
             probe(0)
         # obs / rewards / done are views of the current buffer set (see `obs_buffers`)
         done = self.done_b
-        if self._encoded:
+        if self._use_ep:
+            info = self._step_ep(actions, prog, stream, probe)
+        elif self._encoded:
             if self.fused_step and not self._hetero:
                 # the step and every agent's encoded view, one call (mg_step_encode_views)
                 N.check(self._lib.mg_step_encode_views(C.byref(self._cfg), C.byref(self._state), actions.data_ptr(),
@@ -1325,7 +1375,43 @@ class MultiGridEnv(object):
             probe(2)
         if self.strict == "sync":
             self.check_errors()
-        return self._package_obs(), self.rewards, done, {}
+        return self._package_obs(), self.rewards, done, (info if self._use_ep else {})
+
+    def _step_ep(self, actions, prog, stream, probe):
+        """step()'s launches with an MgEpisode (episode_info and / or auto_reset="next_step"): the branches of step(), each
+        through the _ep twin of its call.  Returns the info dict of the current buffer set."""
+        import torch
+        L, r = self._lib, self._ring[self._ring_i]
+        ep = C.byref(r["ep"])
+        cfg, st = C.byref(self._cfg), C.byref(self._state)
+        a, ab, rew = actions.data_ptr(), actions.element_size(), self.rewards.data_ptr()
+        fused = self.fused_step and not self._hetero
+        if self._encoded and fused:
+            N.check(L.mg_step_encode_views_ep(cfg, st, a, ab, rew, prog, self.obs.data_ptr(), ep, stream))
+        else:
+            rc = N.E_UNSUPPORTED
+            if fused and self._ep_fused:
+                # (there is no _ep twin of mg_step_render_encode: encode_in_step takes mg_step_render_ep + mg_encode)
+                rc = L.mg_step_render_ep(cfg, st, a, ab, rew, prog, self.obs.data_ptr(), ep, stream)
+                if rc == N.E_UNSUPPORTED:      # (nothing was launched: no instantiation with the episode code for this shape)
+                    self._ep_fused = False
+                else:
+                    N.check(rc)
+            if rc == N.E_UNSUPPORTED:
+                N.check(L.mg_step_ep(cfg, st, a, ab, rew, prog, ep, stream))
+                if probe is not None:
+                    probe(1)
+                for g in self._groups:       # one launch per view group
+                    if self._encoded:
+                        N.check(L.mg_encode_views(C.byref(g.cfg), st, g.obs.data_ptr(), stream))
+                    else:
+                        N.check(L.mg_render_obs(C.byref(g.cfg), st, g.obs.data_ptr(), None, None, None, stream))
+        if self.encode_in_step:
+            self._encode_into(self._encoding_buffer())
+        if not self.episode_info:
+            return {}
+        torch.eq(r["ep_flags"].unsqueeze(0), self._ep_vals, out=r["ep_bits"])
+        return r["info"]
 
     def _render(self, debug=False, group=None):
         import torch
@@ -1582,11 +1668,14 @@ class MultiGridEnv(object):
         sd = {k: getattr(self, k).clone() for k in self._STATE_KEYS}
         if self.prestige_t is not None:
             sd["prestige_t"] = self.prestige_t.clone()
+        if self.ep_return_t is not None:        # episode_info: the running episodes' return accumulators
+            sd["ep_return_t"] = self.ep_return_t.clone()
         sd["version"] = torch.tensor(STATE_DICT_VERSION)
         return sd
 
     def load_state_dict(self, sd):
         want = set(self._STATE_KEYS) | {"version"} | ({"prestige_t"} if self.prestige_t is not None else set())
+        want |= {"ep_return_t"} if self.ep_return_t is not None else set()
         if set(sd.keys()) != want:
             raise KeyError("load_state_dict: expected exactly the keys %s, got %s (a checkpoint without "
                            "'version' / 'mt_head' predates the look-ahead RNG form and cannot be resumed)"

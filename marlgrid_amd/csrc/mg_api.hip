@@ -57,6 +57,15 @@ int check_both(const MgConfig* c, const MgState* s) {
 
 int rc(hipError_t e) { return e == hipSuccess ? MG_OK : MG_E_LAUNCH; }
 
+// MgEpisode (mg_*_ep): what can be said without looking into device memory
+int check_episode(const MgEpisode* ep, const MgGenProgram* auto_reset) {
+    if (!ep) return MG_OK;
+    if (ep->reset_mode != 0 && ep->reset_mode != 1) return MG_E_ARG;
+    if (ep->reset_mode == 1 && !auto_reset) return MG_E_ARG;     // next-step reset resets: it needs the program
+    if (ep->out_return && !ep->ep_return) return MG_E_ARG;
+    return MG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -119,6 +128,20 @@ int32_t mg_reset(const MgConfig* cfg, const MgState* st, const MgGenProgram* pro
     return rc(mg::launch_reset(*cfg, *st, *prog, env_mask, (hipStream_t)stream));
 }
 
+int32_t mg_episode_struct_size(void) { return (int32_t)sizeof(MgEpisode); }
+
+int32_t mg_step_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
+                   const MgGenProgram* auto_reset, const MgEpisode* ep, void* stream) {
+    int e = check_episode(ep, auto_reset);      // (first: answered without a valid config or a device)
+    if (e) return e;
+    e = check_both(cfg, st);
+    if (e) return e;
+    if (!actions || !rewards) return MG_E_ARG;
+    if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return MG_E_ARG;
+    if (auto_reset && (e = check_prog(cfg, auto_reset))) return e;
+    return rc(mg::launch_step(*cfg, *st, actions, action_bytes, rewards, auto_reset, (hipStream_t)stream, ep));
+}
+
 int32_t mg_step(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
                 const MgGenProgram* auto_reset, void* stream) {
     int e = check_both(cfg, st);
@@ -138,14 +161,18 @@ int32_t mg_render_obs(const MgConfig* cfg, const MgState* st, uint8_t* obs, uint
 }
 
 static int32_t step_render(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
-                           const MgGenProgram* auto_reset, uint8_t* obs, uint8_t* encode_out, void* stream) {
-    int e = check_both(cfg, st);
+                           const MgGenProgram* auto_reset, uint8_t* obs, uint8_t* encode_out, void* stream,
+                           const MgEpisode* ep = nullptr) {
+    int e = check_episode(ep, auto_reset);
+    if (e) return e;
+    e = check_both(cfg, st);
     if (e) return e;
     if (!actions || !rewards || !obs) return MG_E_ARG;
     if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return MG_E_ARG;
     if (cfg->n_view != 0) return MG_E_ARG;   // one launch steps AND renders every agent: view groups take mg_step + mg_render_obs
     if (auto_reset && (e = check_prog(cfg, auto_reset))) return e;
     if (encode_out && !mg::render_can_encode(*cfg)) return MG_E_UNSUPPORTED;
+    if (ep && !mg::render_can_episode(*cfg)) return MG_E_UNSUPPORTED;
     mg::FusedStep fs;
     fs.actions = actions;
     fs.rewards = rewards;
@@ -159,12 +186,19 @@ static int32_t step_render(const MgConfig* cfg, const MgState* st, const void* a
     fs.enc_m_cells = (uint32_t)((0x100000000ull + cells - 1) / cells);
     fs.enc_m_n = (uint32_t)((0x100000000ull + n - 1) / n);
     fs.enc_ne = 0;        // (launch_render fills it in for the instantiations that use it)
+    fs.has_ep = ep ? 1 : 0;
+    fs.ep = ep ? *ep : MgEpisode{};
     return rc(mg::launch_render(*cfg, *st, obs, nullptr, nullptr, nullptr, (hipStream_t)stream, &fs));
 }
 
 int32_t mg_step_render(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
                        const MgGenProgram* auto_reset, uint8_t* obs, void* stream) {
     return step_render(cfg, st, actions, action_bytes, rewards, auto_reset, obs, nullptr, stream);
+}
+
+int32_t mg_step_render_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
+                          const MgGenProgram* auto_reset, uint8_t* obs, const MgEpisode* ep, void* stream) {
+    return step_render(cfg, st, actions, action_bytes, rewards, auto_reset, obs, nullptr, stream, ep);
 }
 
 int32_t mg_step_render_encode(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
@@ -198,6 +232,20 @@ int32_t mg_step_encode_views(const MgConfig* cfg, const MgState* st, const void*
     if (cfg->n_view != 0) return MG_E_ARG;   // as mg_step_render: view groups take mg_step + mg_encode_views per group
     if (auto_reset && (e = check_prog(cfg, auto_reset))) return e;
     return rc(mg::launch_step_encode_views(*cfg, *st, actions, action_bytes, rewards, auto_reset, views, (hipStream_t)stream));
+}
+
+int32_t mg_step_encode_views_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes,
+                                float* rewards, const MgGenProgram* auto_reset, uint8_t* views, const MgEpisode* ep,
+                                void* stream) {
+    int e = check_episode(ep, auto_reset);
+    if (e) return e;
+    e = check_both(cfg, st);
+    if (e) return e;
+    if (!actions || !rewards || !views) return MG_E_ARG;
+    if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return MG_E_ARG;
+    if (cfg->n_view != 0) return MG_E_ARG;   // as mg_step_encode_views
+    if (auto_reset && (e = check_prog(cfg, auto_reset))) return e;
+    return rc(mg::launch_step_encode_views(*cfg, *st, actions, action_bytes, rewards, auto_reset, views, (hipStream_t)stream, ep));
 }
 
 int32_t mg_put_obj(const MgConfig* cfg, const MgState* st, int32_t obj, int32_t x, int32_t y,

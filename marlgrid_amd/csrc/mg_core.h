@@ -513,6 +513,9 @@ struct StepScratch {        // per-workgroup arrays, this env is column `col`, e
     uint8_t* ordp = nullptr;
     int32_t* psc = nullptr;
     uint64_t* rec_out = nullptr;
+    // the mg_*_ep entry points: reset mode and the episode outputs (marlgrid_hip.h MgEpisode); null: the plain step
+    const MgEpisode* ep = nullptr;
+    const float* ep_rewards = nullptr;     // ... and the step's rewards array (step_end reads this step's rewards back for the return)
 #if defined(MG_AB_VARIANTS)
     unsigned long long* stamp = nullptr;   // measurement build: 5 words, wall_clock64 at the section ends of step_run (or null)
 #endif
@@ -598,7 +601,16 @@ struct StepCtx {            // what an env's step carries from part to part (one
     int err, step_count;
     MtAhead ahead;
     bool grid_dirty;
+    bool pending;           // next-step reset: the episode had ended when this call began — the call is the env's reset
 };
+// Next-step reset: "the episode has ended" read off the state the last call left (the done flags rotate through the
+// host's buffers, the state does not): the time limit, or every agent done (base.py:649) — records in rec[.][col].
+MG_HD bool episode_ended(const MgConfig& cfg, const uint64_t* rec, int S, int col, int step_count) {
+    if (step_count >= cfg.max_steps) return true;
+    for (int k = 0; k < cfg.n_agents; k++)
+        if (!(rec_byte(rec[k * S + col], MG_AG_FLAGS) & MG_AF_DONE)) return false;
+    return true;
+}
 
 MG_HD StepCtx step_begin(const MgConfig& cfg, const MgState& st, int b, const StepEnv& env, const StepScratch& sc, uint8_t* g) {
     const int n = cfg.n_agents, W = cfg.W, H = cfg.H, S = sc.S, col = sc.col;
@@ -610,7 +622,16 @@ MG_HD StepCtx step_begin(const MgConfig& cfg, const MgState& st, int b, const St
     c.mt.ahead_regs = !sc.defer_writeback;       // (defer_writeback: the obs kernel's fused step)
     c.err = 0;
     c.grid_dirty = false;
+    c.pending = false;
     MG_STEP_STAMP(0);
+    if (sc.ep && sc.ep->reset_mode == 1 && episode_ended(cfg, s_rec, S, col, env.sc0)) {
+        // this call resets the env (step_end): nothing spawns, nothing is shuffled, nobody acts
+        c.pending = true;
+        c.step_count = env.sc0;
+        c.order = 0;
+        c.ahead = mt_ahead(c.mt);       // (nothing drawn: requests nothing)
+        return c;
+    }
 
     // late spawns (base.py:503-506), before step_count is incremented and before the shuffle: any agent
     // that is neither active nor done (spawn_delay not reached at reset, or lifted off the grid by a
@@ -671,6 +692,10 @@ MG_HD StepCtx step_begin(const MgConfig& cfg, const MgState& st, int b, const St
 MG_HD void step_agents(const MgConfig& cfg, const MgState& st, float* rewards, int b, const StepScratch& sc, uint8_t* g, StepCtx& c) {
     const int n = cfg.n_agents, W = cfg.W, H = cfg.H, S = sc.S, col = sc.col;
     uint64_t* s_rec = sc.rec;
+    if (c.pending) {                // next-step reset: the action row is ignored, every reward is 0
+        for (int k = 0; k < n; k++) rewards[(size_t)b * n + k] = 0.0f;
+        return;
+    }
     const bool direct = !sc.fb;     // (no pre-loaded front cells: the action loop reads `g`)
     int err = c.err;
     bool grid_dirty = c.grid_dirty;
@@ -784,7 +809,7 @@ MG_HD StepOut step_end(const MgConfig& cfg, const MgState& st, const MgGenProgra
     // (agent.reset(new_episode=False), agents.py:161-166) and are re-placed by rejection sampling
     // among the agents currently on the grid.  Then episode done (base.py:649).
     bool all_done = true;
-    for (int k = 0; k < n; k++) {
+    for (int k = 0; k < n && !c.pending; k++) {
         uint64_t r = s_rec[k * S + col];
         const uint32_t f = rec_byte(r, MG_AG_FLAGS);
         if (f & MG_AF_DONE) {
@@ -799,8 +824,26 @@ MG_HD StepOut step_end(const MgConfig& cfg, const MgState& st, const MgGenProgra
             }
         } else all_done = false;
     }
-    const bool done = (step_count >= cfg.max_steps) || all_done;
-    if (done && auto_reset) {
+    const bool done = !c.pending && ((step_count >= cfg.max_steps) || all_done);
+    const bool next_step = sc.ep && sc.ep->reset_mode == 1;
+    const bool resets = next_step ? c.pending : (done && auto_reset);
+    if (sc.ep) {
+        // the episode as it stands BEFORE any reset: length (base.py:512), why it ended (base.py:649), the return — this
+        // step's float32 rewards (written by step_agents / step_par_commit, this wave) added in float64 to the accumulator,
+        // which a reset leaves at 0
+        const MgEpisode& ep = *sc.ep;
+        if (ep.out_length) ep.out_length[b] = c.pending ? 0 : step_count;
+        if (ep.out_flags)
+            ep.out_flags[b] = (uint8_t)(c.pending ? MG_EPF_RESET : !done ? 0 : all_done ? MG_EPF_TERMINATED : MG_EPF_TRUNCATED);
+        if (ep.ep_return)
+            for (int k = 0; k < n; k++) {
+                const size_t at = (size_t)b * n + k;
+                const double sum = c.pending ? 0.0 : ep.ep_return[at] + (double)sc.ep_rewards[at];
+                if (ep.out_return) ep.out_return[at] = sum;
+                ep.ep_return[at] = resets ? 0.0 : sum;
+            }
+    }
+    if (resets) {
         const int e2 = reset_env(cfg, st, prog, sc.oflags, b, g, mt, s_rec, S, col);
         err = err ? err : e2;
         step_count = 0;
@@ -855,11 +898,12 @@ struct ParLane {            // what a lane carries from step_par_resolve to step
     bool live, active, moved;
 };
 // sc.pflag [n][8] u8: bit 0 the agent moved, bit 1 its env needs the sequential loop; sc.ordp [n][8] u8: the agent's turn;
-// sc.psc [8] i32: the env's step_count (after the increment)
+// sc.psc [8] i32: the env's step_count (after the increment; -1: the call is the env's next-step reset, its agents resolve
+// to "nothing happened": no record change, reward 0, no request for the loop)
 MG_HD void step_par_publish(const MgConfig& cfg, const StepScratch& sc, const StepCtx& c) {      // the env's lane, after step_begin
     const int n = cfg.n_agents, col = sc.col;
     for (int i = 0; i < n; i++) sc.ordp[(int)((c.order >> (4 * i)) & 0xFull) * 8 + col] = (uint8_t)i;
-    sc.psc[col] = c.step_count;
+    sc.psc[col] = c.pending ? -1 : c.step_count;     // (-1: next-step reset — the env's agents do nothing in this call)
 }
 MG_HD ParLane step_par_resolve(const MgConfig& cfg, const StepScratch& sc, const uint8_t* grids, int kb, int lane) {
     const int n = cfg.n_agents, W = cfg.W, H = cfg.H;
@@ -874,7 +918,7 @@ MG_HD ParLane step_par_resolve(const MgConfig& cfg, const StepScratch& sc, const
     uint64_t r = sc.rec[k * 8 + j];
     const uint32_t flags = rec_byte(r, MG_AG_FLAGS);
     bool serial = false;
-    if (flags & MG_AF_ACTIVE) {
+    if ((flags & MG_AF_ACTIVE) && !(sc.ep && sc.psc[j] < 0)) {
         P.active = true;
         const int action = (int)sc.act[k * 8 + j];
         const int cx = (int)rec_byte(r, MG_AG_X), cy = (int)rec_byte(r, MG_AG_Y), dir = (int)rec_byte(r, MG_AG_DIR);

@@ -63,6 +63,8 @@ struct FusedStep {
     uint32_t enc_m_cells, enc_m_n;   // ... its divide-by-multiply constants: ceil(2^32 / (W * H)), ceil(2^32 / n)
     int32_t enc_ne;           // ... dwords of its LDS table — one per grid byte value: object kinds, then the agent codes n_obj +
                               //     4 k + dir —, (n_obj + 4 n) rounded up to 16 (mg_render.hip: render_enc_entries; 0: none)
+    int32_t has_ep;           // mg_step_render_ep: `ep` is set — the launcher then takes an instantiation with the episode code
+    MgEpisode ep;             //     compiled in (V + 32); the plain ones never look at either
 };
 
 // Block-shared LDS of the obs-render kernel behind the atlas, sized by the configuration (object kinds in sixteens): per

@@ -42,6 +42,8 @@ struct EncViewsStep {
     int32_t has_prog, action_bytes;
     const void* actions;
     float* rewards;
+    int32_t has_ep, reserved0;
+    MgEpisode ep;       // mg_step_encode_views_ep (has_ep)
 };
 
 // LDS of the step phase for E envs (step_kernel's layout with S = E)
@@ -72,6 +74,7 @@ __global__ __launch_bounds__(kBlock) void encode_views_kernel(MgConfig cfg, cons
         sc.oflags = s_oflags;
         sc.S = E;
         sc.col = tid;
+        if (fs.has_ep) { sc.ep = &fs.ep; sc.ep_rewards = fs.rewards; }
         const int b = blockIdx.x * E + tid;
         const bool live = tid < E && b < cfg.B;
         {
@@ -301,7 +304,7 @@ hipError_t launch_encode_views(const MgConfig& cfg, const MgState& st, uint8_t* 
 }
 
 hipError_t launch_step_encode_views(const MgConfig& cfg, const MgState& st, const void* actions, int action_bytes,
-                                    float* rewards, const MgGenProgram* prog, uint8_t* out, hipStream_t s) {
+                                    float* rewards, const MgGenProgram* prog, uint8_t* out, hipStream_t s, const MgEpisode* ep) {
     EncViewsStep fs{};
     fs.st = st;
     fs.actions = actions;
@@ -309,10 +312,12 @@ hipError_t launch_step_encode_views(const MgConfig& cfg, const MgState& st, cons
     fs.rewards = rewards;
     fs.has_prog = prog ? 1 : 0;
     if (prog) fs.prog = *prog;
+    fs.has_ep = ep ? 1 : 0;
+    if (ep) fs.ep = *ep;
     const hipError_t e = launch_encode_views(cfg, st, out, s, &fs);
     if (e != hipErrorNotSupported) return e;
     // no workgroup of whole envs fits (many agents with a large view): the step, then the views
-    const hipError_t e1 = launch_step(cfg, st, actions, action_bytes, rewards, prog, s);
+    const hipError_t e1 = launch_step(cfg, st, actions, action_bytes, rewards, prog, s, ep);
     if (e1 != hipSuccess) return e1;
     return launch_encode_views(cfg, st, out, s, nullptr);
 }

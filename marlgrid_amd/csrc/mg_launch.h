@@ -10,7 +10,7 @@ hipError_t launch_mt_seed(int B, const uint32_t* keys, const int32_t* key_len, u
 hipError_t launch_reset(const MgConfig& cfg, const MgState& st, const MgGenProgram& prog, const uint8_t* mask,
                         hipStream_t s);
 hipError_t launch_step(const MgConfig& cfg, const MgState& st, const void* actions, int action_bytes,
-                       float* rewards, const MgGenProgram* auto_reset, hipStream_t s);
+                       float* rewards, const MgGenProgram* auto_reset, hipStream_t s, const MgEpisode* ep = nullptr);
 struct FusedStep;
 // which instantiation of mg::render_kernel<VS, TS, WPB, V, RM> a configuration gets (0 = the value is read from the
 // config at run time) and the LDS bytes of one of its workgroups: filled in INSTEAD of launching when handed to launch_render
@@ -19,6 +19,7 @@ hipError_t launch_render(const MgConfig& cfg, const MgState& st, uint8_t* obs, u
                          uint8_t* view_agent, uint8_t* vis_mask, hipStream_t s, const FusedStep* fused_step = nullptr,
                          RenderPick* pick = nullptr);
 int render_min_lds_bytes(const MgConfig& cfg);
+bool render_can_episode(const MgConfig& cfg);     // mg_step_render_ep: this configuration has a step launch with the episode outputs
 bool render_can_encode(const MgConfig& cfg);      // mg_step_render_encode: this configuration's step launch can write the encoding too
 hipError_t launch_encode(const MgConfig& cfg, const MgState& st, const uint8_t* vis_mask, uint8_t* out,
                          hipStream_t s);
@@ -27,7 +28,8 @@ struct EncViewsStep;
 hipError_t launch_encode_views(const MgConfig& cfg, const MgState& st, uint8_t* out, hipStream_t s, const EncViewsStep* fs = nullptr);
 // mg_step_encode_views: the step and the views in one launch where a workgroup of whole envs fits, else the two launches
 hipError_t launch_step_encode_views(const MgConfig& cfg, const MgState& st, const void* actions, int action_bytes,
-                                    float* rewards, const MgGenProgram* prog, uint8_t* out, hipStream_t s);
+                                    float* rewards, const MgGenProgram* prog, uint8_t* out, hipStream_t s,
+                                    const MgEpisode* ep = nullptr);
 hipError_t launch_put_obj(const MgConfig& cfg, const MgState& st, int obj, int x, int y, const uint8_t* mask,
                           hipStream_t s);
 hipError_t launch_place(const MgConfig& cfg, const MgState& st, int what, int x0, int y0, int x1, int y1, int max_tries,

@@ -16,6 +16,7 @@ extern "C" int mg_ab_stamps(unsigned long long* p) { g_ab_stamps = p; return 0; 
 #if !defined(MG_DEV_ONLY)
 MG_RENDER_GROUP_A(MG_RENDER_EXTERN)
 MG_RENDER_GROUP_N(MG_RENDER_EXTERN)
+MG_RENDER_GROUP_P(MG_RENDER_EXTERN)
 MG_RENDER_GROUP_B(MG_RENDER_EXTERN)
 MG_RENDER_GROUP_C(MG_RENDER_EXTERN)
 MG_RENDER_GROUP_D(MG_RENDER_EXTERN)
@@ -125,6 +126,44 @@ static hipError_t launch_render_enc(const MgConfig& cfg, const MgState& st, uint
                : launch_render_t<0, 8, 4, 16, 0>(cfg, st, obs, nullptr, nullptr, nullptr, s, fs, pick);
 #endif
 }
+// mg_step_render_ep: the instantiations with the episode code compiled in (variant + 32, MG_RENDER_GROUP_P), the shapes and the
+// choice among them as launch_render_enc's.  Everything else is hipErrorNotSupported: nothing is launched, the C ABI answers
+// MG_E_UNSUPPORTED, hosts call mg_step_ep and mg_render_obs.
+static hipError_t launch_render_ep(const MgConfig& cfg, const MgState& st, uint8_t* obs, hipStream_t s, const FusedStep* fs,
+                                   RenderPick* pick) {
+#if defined(MG_DEV_ONLY)
+    return launch_render_t<MG_DEV_ONLY>(cfg, st, obs, nullptr, nullptr, nullptr, s, fs, pick);
+#else
+    if (cfg.prestige_mask || render_big_grid(cfg)) return hipErrorNotSupported;
+    const int vs = cfg.view_size, ts = cfg.tile_size, mode = render_mode_for(cfg), wpb = choose_wpb(cfg, mode);
+    if (render_lds_bytes(cfg, 4, mode) > 160 * 1024) return hipErrorNotSupported;     // (an atlas that stays in global memory)
+    const bool w16 = wpb == 16;
+    if (mode == 2) {
+        if (vs == 7 && ts == 5)
+            return w16 ? launch_render_t<7, 5, 16, 32, 2>(cfg, st, obs, nullptr, nullptr, nullptr, s, fs, pick)
+                       : launch_render_t<7, 5, 4, 32, 2>(cfg, st, obs, nullptr, nullptr, nullptr, s, fs, pick);
+        return hipErrorNotSupported;
+    }
+    if (ts != 8) return hipErrorNotSupported;
+    if (vs == 7)
+        return w16 ? launch_render_t<7, 8, 16, 32, 0>(cfg, st, obs, nullptr, nullptr, nullptr, s, fs, pick)
+                   : launch_render_t<7, 8, 4, 32, 0>(cfg, st, obs, nullptr, nullptr, nullptr, s, fs, pick);
+    if (vs == 9)
+        return w16 ? launch_render_t<9, 8, 16, 32, 0>(cfg, st, obs, nullptr, nullptr, nullptr, s, fs, pick)
+                   : launch_render_t<9, 8, 4, 32, 0>(cfg, st, obs, nullptr, nullptr, nullptr, s, fs, pick);
+    if (vs <= 9) return hipErrorNotSupported;
+    // (run-time view size: 8-wave workgroups, as MG_RENDER_DISPATCH_RT)
+    return w16 ? launch_render_t<0, 8, 8, 32, 0>(cfg, st, obs, nullptr, nullptr, nullptr, s, fs, pick)
+               : launch_render_t<0, 8, 4, 32, 0>(cfg, st, obs, nullptr, nullptr, nullptr, s, fs, pick);
+#endif
+}
+bool render_can_episode(const MgConfig& cfg) {
+    FusedStep f;
+    f.enabled = 1;
+    f.has_ep = 1;
+    RenderPick p;
+    return launch_render_ep(cfg, MgState{}, nullptr, nullptr, &f, &p) == hipSuccess;
+}
 bool render_can_encode(const MgConfig& cfg) {
     FusedStep f;
     f.enabled = 1;
@@ -151,7 +190,13 @@ hipError_t launch_render(const MgConfig& cfg, const MgState& st, uint8_t* obs, u
     none.encode_out = nullptr;
     none.enc_m_cells = none.enc_m_n = 0;
     none.enc_ne = 0;
+    none.has_ep = 0;
+    none.ep = MgEpisode{};
     if (!fs) fs = &none;
+    if (fs->has_ep) {
+        if (view_cells || view_agent || vis_mask || pick || fs->encode_out) return hipErrorInvalidValue;
+        return launch_render_ep(cfg, st, obs, s, fs, nullptr);
+    }
     if (fs->encode_out) {
         if (view_cells || view_agent || vis_mask || pick) return hipErrorInvalidValue;
         return launch_render_enc(cfg, st, obs, s, fs, nullptr);

@@ -244,6 +244,8 @@ extern unsigned long long* g_ab_stamps;       // set through mg_ab_stamps (mg_re
 // VX_ = V_ + 16: mg_step_render_encode's instantiations — the fused step also writes MultiGrid.encode of its batch (compiled
 //     in, not a flag of the launch: with the code in every instantiation the launches that do not ask for it lost 0.4 - 1.4 %
 //     off the fast path — `profiles/r06/ab_fused_encode_in_launch_as_a_flag_v23.txt`).
+// VX_ = V_ + 32: mg_step_render_ep's instantiations — the fused step takes its reset mode from an MgEpisode and writes the
+//     episode outputs (compiled in for the same reason; profiles/episodes/README.md: the plain ones keep their resources).
 template <int VS_, int TS_, int WPB, int VX_ = 0, int RM_ = 0>
 __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState st, uint8_t* __restrict__ obs,
                                                         uint8_t* __restrict__ dbg_cells,
@@ -251,6 +253,7 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                                                         uint8_t* __restrict__ dbg_vis, RenderLaunch lc, FusedStep fs) {
     constexpr int V_ = VX_ & 15;                // the variant proper
     constexpr bool kEnc = (VX_ & 16) != 0;      // + 16: mg_step_render_encode
+    constexpr bool kEp = (VX_ & 32) != 0;       // + 32: mg_step_render_ep — reset mode and episode outputs (MgEpisode) in the fused step
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     // the wave index is uniform: told to the compiler, everything derived from it (the wave's scratch
     // pointers, its run of envs, loop bounds) lives in SGPRs instead of one VGPR each
@@ -633,6 +636,8 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                 // one-round-trip head refills through LDS-DMA (mt_generate16_dma): their landing zone, 9 rows of 128 bytes,
                 // is the tmap area — the views have not begun
                 sc.dma = (size_t)L.tmap_slots * L.tmap_stride >= kMtDmaBufDwords * 4 ? reinterpret_cast<uint32_t*>(w_tmap0) : nullptr;
+                // (mg_step_render_ep: a template value, not a branch — with it the plain instantiations stay at their register budget)
+                if constexpr (kEp) { sc.ep = &fs.ep; sc.ep_rewards = fs.rewards; }
                 // The step in three parts (mg_core.h): step_begin on the env's lane (late spawns, the shuffle); the agents
                 // resolved by ONE LANE PER (agent, env) on the pre-step state — lane 8 k + j: agent k of staged env j, up
                 // to 8 agents — instead of a sequential loop of ~1 700 dependent instructions on the env's lane, which then
@@ -1487,6 +1492,9 @@ hipError_t launch_render_t(const MgConfig& cfg, const MgState& st, uint8_t* obs,
 #define MG_RENDER_GROUP_N(X) /* mg_step_render_encode (V + 16): the BASELINE configs' shapes, the default tile, any view at tile 8 */ \
     X(7, 8, 16, 16, 0) X(7, 8, 4, 16, 0) X(9, 8, 16, 16, 0) X(9, 8, 4, 16, 0) X(0, 8, 8, 16, 0) X(0, 8, 4, 16, 0)                       \
     X(7, 5, 16, 16, 2) X(7, 5, 4, 16, 2)
+#define MG_RENDER_GROUP_P(X) /* mg_step_render_ep (V + 32): the shapes of group N */                                       \
+    X(7, 8, 16, 32, 0) X(7, 8, 4, 32, 0) X(9, 8, 16, 32, 0) X(9, 8, 4, 32, 0) X(0, 8, 8, 32, 0) X(0, 8, 4, 32, 0)                       \
+    X(7, 5, 16, 32, 2) X(7, 5, 4, 32, 2)
 #define MG_RENDER_EXTERN(VS, TS, WPB, V, RM)                                                                               \
     extern template hipError_t launch_render_t<VS, TS, WPB, V, RM>(const MgConfig&, const MgState&, uint8_t*, uint8_t*,     \
                                                                  uint8_t*, uint8_t*, hipStream_t, const FusedStep*, RenderPick*);

@@ -26,7 +26,7 @@ namespace mg {
 template <int BS>
 __global__ __launch_bounds__(BS) void step_kernel(MgConfig cfg, MgState st, MgGenProgram prog, int has_prog,
                                                   const void* __restrict__ actions, int action_bytes,
-                                                  float* __restrict__ rewards) {
+                                                  float* __restrict__ rewards, int has_ep, MgEpisode ep) {
     extern __shared__ __attribute__((aligned(16))) uint64_t s_mem[];
     const int n = cfg.n_agents;
     StepScratch sc;
@@ -42,6 +42,7 @@ __global__ __launch_bounds__(BS) void step_kernel(MgConfig cfg, MgState st, MgGe
     sc.S = BS;
     const int tid = threadIdx.x;
     sc.col = tid;
+    if (has_ep) { sc.ep = &ep; sc.ep_rewards = rewards; }      // mg_step_ep (a launch-uniform branch)
     const int b = blockIdx.x * BS + tid;
     const bool live = b < cfg.B;
 
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(BS) void step_kernel(MgConfig cfg, MgState st, MgGe
 
 template <int BS>
 static hipError_t launch_step_bs(const MgConfig& cfg, const MgState& st, const void* actions, int action_bytes,
-                                 float* rewards, const MgGenProgram* prog, hipStream_t s) {
+                                 float* rewards, const MgGenProgram* prog, const MgEpisode* ep, hipStream_t s) {
     dim3 grid((cfg.B + BS - 1) / BS), block(BS);
     const size_t lds = (size_t)cfg.n_agents * BS * (sizeof(uint64_t) + 4) + MG_MAX_OBJ * sizeof(MgObjDesc) +
                        (size_t)MG_MT_HEAD * BS * sizeof(uint32_t) + MG_MAX_OBJ;
@@ -74,12 +75,13 @@ static hipError_t launch_step_bs(const MgConfig& cfg, const MgState& st, const v
     const MgGenProgram& p = prog ? *prog : none;
     const int has = prog ? 1 : 0;
     if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((step_kernel<BS>), grid, block, lds, s, cfg, st, p, has, actions, action_bytes, rewards);
+    hipLaunchKernelGGL((step_kernel<BS>), grid, block, lds, s, cfg, st, p, has, actions, action_bytes, rewards, ep ? 1 : 0,
+                       ep ? *ep : MgEpisode{});
     return hipGetLastError();
 }
 
 hipError_t launch_step(const MgConfig& cfg, const MgState& st, const void* actions, int action_bytes,
-                       float* rewards, const MgGenProgram* prog, hipStream_t s) {
+                       float* rewards, const MgGenProgram* prog, hipStream_t s, const MgEpisode* ep) {
     if (cfg.B <= 0) return hipSuccess;
     // One lane per env: spread the envs over as many CUs as possible with single-wave workgroups
     // until the batch alone fills the chip several times over.
@@ -89,8 +91,8 @@ hipError_t launch_step(const MgConfig& cfg, const MgState& st, const void* actio
 #if defined(MG_AB_VARIANTS)
     if (const char* f = getenv("MG_STEP_BLOCK")) { const int v = atoi(f); if (v == 64 || v == 256) bs = v; }
 #endif
-    if (bs == 256) return launch_step_bs<256>(cfg, st, actions, action_bytes, rewards, prog, s);
-    return launch_step_bs<64>(cfg, st, actions, action_bytes, rewards, prog, s);
+    if (bs == 256) return launch_step_bs<256>(cfg, st, actions, action_bytes, rewards, prog, ep, s);
+    return launch_step_bs<64>(cfg, st, actions, action_bytes, rewards, prog, ep, s);
 }
 
 }  // namespace mg

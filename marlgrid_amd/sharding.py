@@ -143,7 +143,8 @@ class ShardPipeline(object):
 
     def step(self, actions):
         """actions: (batch_size, n_agents), resident and ready (the parts' streams do not wait for the stream that
-        produced it), or a list with one tensor per part.  Returns per part (obs, rewards, done, info), each ordered on
+        produced it), or a list with one tensor per part.  Returns per part (obs, rewards, done, info) — info: the part's
+        episode_info dict, or {} —, each ordered on
         streams[k]."""
         per_part = isinstance(actions, (list, tuple))
         return self._each(lambda k, env: env.step(actions[k] if per_part else self.part(k, actions)))

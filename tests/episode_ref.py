@@ -66,8 +66,9 @@ class EpisodeOracle(object):
             return [np.stack([p[k] for p in per]) for k in range(self.n)]
         return np.stack([np.stack(p) for p in per])
 
-    def step(self, actions):
-        """-> obs (or None), rewards float64 (B, n), done (B,), info dict as MultiGridEnv.step(episode_info=True) returns it"""
+    def step(self, actions, render=True):
+        """-> obs (or None), rewards float64 (B, n), done (B,), info dict as MultiGridEnv.step(episode_info=True) returns it.
+        render=False: obs is None for this call (a caller that does not look at every step); nothing else changes"""
         B, n = self.B, self.n
         a = np.ascontiguousarray(actions, np.int32).reshape(B, n)
         live = np.nonzero(~self.pending)[0]
@@ -117,7 +118,7 @@ class EpisodeOracle(object):
                 self.pending[b] = True
             elif self.mode == "same_step":
                 self._reset_env(b)
-        return self.obs(), rew, done, info
+        return (self.obs() if render else None), rew, done, info
 
 
 def assert_info(got, want, what):

@@ -554,6 +554,30 @@ class MultiGridEnv(object):
             return cls(agents=team, batch_size=batch_size, seeds=seeds, device=device, **kwargs)
         return ShardPipeline(make_part, batch_size, parts=parts, seed=seed, device=device, streams=streams)
 
+    @classmethod
+    def sharded(cls, agents, devices, batch_size=1, seed=1337, streams=None, **kwargs):
+        """The batch as one env of this class per entry of `devices`, in this process (marlgrid_amd.sharding.DeviceShards:
+        shard k owns `shard_range(batch_size, k, len(devices))` on devices[k] and its own stream; entries may repeat).  Shard
+        0 is built with `agents` themselves, the other shards with shallow copies (a learner's networks and buffers are
+        shared, the binding to an env — agent.pos, .dir, ... — is per shard).  A device named m > 1 times gives its shards
+        `share=m` in `place_obs`; every other kwarg reaches every shard unchanged."""
+        import copy
+        from .sharding import DeviceShards, merge_share
+        if "seeds" in kwargs:
+            raise ValueError("sharded(): per-env seeds come from `seed` + the env's index in the whole batch")
+        if kwargs.pop("device", None) is not None:
+            raise ValueError("sharded(): the shards' devices are `devices`; `device` has no meaning next to it")
+        agents = list(agents)
+        place_obs = kwargs.pop("place_obs", True)
+        made = []
+
+        def make_shard(batch_size, seeds, device, share=1):
+            team = agents if not made else [copy.copy(a) for a in agents]
+            made.append(True)
+            return cls(agents=team, batch_size=batch_size, seeds=seeds, device=device, place_obs=merge_share(place_obs, share),
+                       **kwargs)
+        return DeviceShards(make_shard, batch_size, devices, seed=seed, streams=streams)
+
     # ---- configuration ----------------------------------------------------------------------------
     def add_agent(self, agent_interface):
         if isinstance(agent_interface, dict):

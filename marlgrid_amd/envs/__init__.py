@@ -34,17 +34,38 @@ def register_marl_env(env_name, env_class, n_agents, grid_size, view_size, view_
     registered_envs.append(env_name)
 
 
-def make(env_name, pipeline=None, **kwargs):
+def make(env_name, pipeline=None, devices=None, **kwargs):
     """`gym.make` stand-in; kwargs (batch_size, device, seed, seeds, auto_reset, strict, ...) reach the env.
 
     pipeline=P (P >= 2): the batch as P independent envs of batch_size / P on P streams — a
     `marlgrid_amd.sharding.ShardPipeline` whose parts a sampler steps in turn (`pipe.step_part(k, actions)` under
     `pipe.on(k)`): the launches of independent shards overlap (+10 % at 32 768 envs, +17 % at 65 536 on one
-    MI355X), and env g of the batch keeps its seed `seed + g`, so trajectories are those of the one big env."""
+    MI355X), and env g of the batch keeps its seed `seed + g`, so trajectories are those of the one big env.
+
+    devices=[...] (torch devices, strs or ints; entries may repeat): the batch sharded over these devices in ONE process
+    — a `marlgrid_amd.sharding.DeviceShards`: shard k is an env of `shard_range(batch_size, k, len(devices))` on
+    devices[k] with its own stream, `step(actions)` issues every shard's launch from the calling thread, `gather()` joins
+    what they return; env g keeps its seed `seed + g`.  Every other kwarg reaches every shard's env unchanged, except that
+    a device named m > 1 times gives its shards `share=m` in `place_obs`.  Not together with `pipeline`, `seeds` or
+    `device`."""
     try:
         factory = _registry[env_name]
     except KeyError:
         raise KeyError("unknown env id %r; registered: %s" % (env_name, ", ".join(registered_envs))) from None
+    if devices is not None:
+        from ..sharding import DeviceShards, merge_share
+        if pipeline is not None:
+            raise ValueError("make(devices=) and make(pipeline=) are two ways to split one batch: give one of them")
+        if "seeds" in kwargs:
+            raise ValueError("make(devices=): per-env seeds come from `seed` + the env's index in the whole batch")
+        if kwargs.get("device") is not None:
+            raise ValueError("make(devices=): the shards' devices are `devices`; `device` has no meaning next to it")
+        kwargs.pop("device", None)
+        batch_size, seed, streams = kwargs.pop("batch_size", 1), kwargs.pop("seed", 1337), kwargs.pop("streams", None)
+        place_obs = kwargs.pop("place_obs", True)
+        return DeviceShards(lambda batch_size, seeds, device, share=1: factory(
+            batch_size=batch_size, seeds=seeds, device=device, place_obs=merge_share(place_obs, share), **kwargs),
+            batch_size, devices, seed=seed, streams=streams)
     if pipeline is None or int(pipeline) <= 1:
         return factory(**kwargs)
     from ..sharding import ShardPipeline

@@ -1350,92 +1350,65 @@ class MultiGridEnv(object):
             probe(0)
         # obs / rewards / done are views of the current buffer set (see `obs_buffers`)
         done = self.done_b
-        if self._use_ep:
-            info = self._step_ep(actions, prog, stream, probe)
-        elif self._encoded:
-            if self.fused_step and not self._hetero:
-                # the step and every agent's encoded view, one call (mg_step_encode_views)
-                N.check(self._lib.mg_step_encode_views(C.byref(self._cfg), C.byref(self._state), actions.data_ptr(),
-                                                       actions.element_size(), self.rewards.data_ptr(), prog,
-                                                       self.obs.data_ptr(), stream))
-            else:
-                N.check(self._lib.mg_step(C.byref(self._cfg), C.byref(self._state), actions.data_ptr(),
-                                          actions.element_size(), self.rewards.data_ptr(), prog, stream))
-                if probe is not None:
-                    probe(1)
-                for g in self._groups:       # one launch per view group
-                    N.check(self._lib.mg_encode_views(C.byref(g.cfg), C.byref(self._state), g.obs.data_ptr(), stream))
-            if self.encode_in_step:
-                self._encode_into(self._encoding_buffer())
-        elif self.fused_step and not self._hetero:
-            # the whole step — action loop, reset of finished episodes, observation raster — is ONE launch:
-            # the wave that renders an env steps it first
-            enc_rc = N.E_UNSUPPORTED
-            if self.encode_in_step and self._enc_fused:
-                enc_rc = self._lib.mg_step_render_encode(C.byref(self._cfg), C.byref(self._state), actions.data_ptr(),
-                                                         actions.element_size(), self.rewards.data_ptr(), prog,
-                                                         self.obs.data_ptr(), self._encoding_buffer().data_ptr(), stream)
-                if enc_rc == N.E_UNSUPPORTED:      # (nothing was launched: more than 256 object ids + agent marks, or a grid read in place)
-                    self._enc_fused = False
-                else:
-                    N.check(enc_rc)
-            if enc_rc == N.E_UNSUPPORTED:
-                N.check(self._lib.mg_step_render(C.byref(self._cfg), C.byref(self._state), actions.data_ptr(),
-                                                 actions.element_size(), self.rewards.data_ptr(), prog,
-                                                 self.obs.data_ptr(), stream))
-                if self.encode_in_step:
-                    self._encode_into(self._encoding_buffer())
-        else:
-            N.check(self._lib.mg_step(C.byref(self._cfg), C.byref(self._state), actions.data_ptr(),
-                                      actions.element_size(), self.rewards.data_ptr(), prog, stream))
-            if probe is not None:
-                probe(1)
-            for g in self._groups:       # one raster launch per view group (one group unless the agents' views differ)
-                N.check(self._lib.mg_render_obs(C.byref(g.cfg), C.byref(self._state), g.obs.data_ptr(), None,
-                                                None, None, stream))
-            if self.encode_in_step:
-                self._encode_into(self._encoding_buffer())
+        r = self._ring[self._ring_i] if self._use_ep else None
+        self._launch_step(actions, prog, stream, probe, None if r is None else C.byref(r["ep"]))
+        info = {}
+        if self.episode_info:
+            torch.eq(r["ep_flags"].unsqueeze(0), self._ep_vals, out=r["ep_bits"])
+            info = r["info"]        # the info dict of the current buffer set
         if probe is not None:
             probe(2)
         if self.strict == "sync":
             self.check_errors()
-        return self._package_obs(), self.rewards, done, (info if self._use_ep else {})
+        return self._package_obs(), self.rewards, done, info
 
-    def _step_ep(self, actions, prog, stream, probe):
-        """step()'s launches with an MgEpisode (episode_info and / or auto_reset="next_step"): the branches of step(), each
-        through the _ep twin of its call.  Returns the info dict of the current buffer set."""
-        import torch
-        L, r = self._lib, self._ring[self._ring_i]
-        ep = C.byref(r["ep"])
-        cfg, st = C.byref(self._cfg), C.byref(self._state)
-        a, ab, rew = actions.data_ptr(), actions.element_size(), self.rewards.data_ptr()
+    def _launch_step(self, actions, prog, stream, probe, ep):
+        """The step and the observations it returns: fused, if this configuration still can, else mg_step[_ep] and one launch
+        per view group; then mg_encode unless the launch wrote the encoding too.  `ep`: None, or the buffer set's MgEpisode
+        (episode_info and / or auto_reset="next_step") — every call is then the _ep twin of the one it would be."""
+        L, cfg, st = self._lib, C.byref(self._cfg), C.byref(self._state)
+        head = (cfg, st, actions.data_ptr(), actions.element_size(), self.rewards.data_ptr(), prog)
+        tail = (stream,) if ep is None else (ep, stream)
         fused = self.fused_step and not self._hetero
-        if self._encoded and fused:
-            N.check(L.mg_step_encode_views_ep(cfg, st, a, ab, rew, prog, self.obs.data_ptr(), ep, stream))
+        encoding_written = False
+        rc = None       # the fused call's answer.  (MG_E_UNSUPPORTED: nothing was launched, this configuration has no such instantiation)
+        if fused and self._encoded:
+            # the step and every agent's encoded view, one call
+            rc = (L.mg_step_encode_views if ep is None else L.mg_step_encode_views_ep)(*head, self.obs.data_ptr(), *tail)
+        elif fused and ep is not None:
+            # (there is no _ep twin of mg_step_render_encode: encode_in_step takes mg_step_render_ep + mg_encode)
+            if self._ep_fused:
+                rc = L.mg_step_render_ep(*head, self.obs.data_ptr(), *tail)
+                if rc == N.E_UNSUPPORTED:
+                    self._ep_fused, rc = False, None
+        elif fused:
+            # the whole step — action loop, reset of finished episodes, observation raster — is ONE launch: the wave that
+            # renders an env steps it first; with encode_in_step it writes MultiGrid.encode of its envs too, unless there are
+            # more than 256 object ids + agent marks, or the grid is read in place, ...
+            if self.encode_in_step and self._enc_fused:
+                rc = L.mg_step_render_encode(*head, self.obs.data_ptr(), self._encoding_buffer().data_ptr(), stream)
+                self._enc_fused = encoding_written = rc != N.E_UNSUPPORTED
+            if not encoding_written:
+                rc = L.mg_step_render(*head, self.obs.data_ptr(), stream)
+        if rc is not None:
+            N.check(rc)
         else:
-            rc = N.E_UNSUPPORTED
-            if fused and self._ep_fused:
-                # (there is no _ep twin of mg_step_render_encode: encode_in_step takes mg_step_render_ep + mg_encode)
-                rc = L.mg_step_render_ep(cfg, st, a, ab, rew, prog, self.obs.data_ptr(), ep, stream)
-                if rc == N.E_UNSUPPORTED:      # (nothing was launched: no instantiation with the episode code for this shape)
-                    self._ep_fused = False
-                else:
-                    N.check(rc)
-            if rc == N.E_UNSUPPORTED:
-                N.check(L.mg_step_ep(cfg, st, a, ab, rew, prog, ep, stream))
-                if probe is not None:
-                    probe(1)
-                for g in self._groups:       # one launch per view group
-                    if self._encoded:
-                        N.check(L.mg_encode_views(C.byref(g.cfg), st, g.obs.data_ptr(), stream))
-                    else:
-                        N.check(L.mg_render_obs(C.byref(g.cfg), st, g.obs.data_ptr(), None, None, None, stream))
-        if self.encode_in_step:
+            N.check((L.mg_step if ep is None else L.mg_step_ep)(*head, *tail))
+            if probe is not None:
+                probe(1)
+            self._launch_views()
+        if self.encode_in_step and not encoding_written:
             self._encode_into(self._encoding_buffer())
-        if not self.episode_info:
-            return {}
-        torch.eq(r["ep_flags"].unsqueeze(0), self._ep_vals, out=r["ep_bits"])
-        return r["info"]
+
+    def _launch_views(self, pixels=False):
+        """one launch per view group (one group unless the agents' views differ) of the current state into the groups'
+        observation buffers — encoded views: mg_encode_views —, or, `pixels`, the raster into their pixel buffers"""
+        st, stream = C.byref(self._state), self._stream()
+        for g in self._groups:
+            if self._encoded and not pixels:
+                N.check(self._lib.mg_encode_views(C.byref(g.cfg), st, g.obs.data_ptr(), stream))
+            else:
+                N.check(self._lib.mg_render_obs(C.byref(g.cfg), st, self._pixel_buffer(g).data_ptr(), None, None, None, stream))
 
     def _render(self, debug=False, group=None):
         import torch
@@ -1449,13 +1422,7 @@ class MultiGridEnv(object):
             N.check(self._lib.mg_render_obs(C.byref(g.cfg), C.byref(self._state), self._pixel_buffer(g).data_ptr(),
                                             cells.data_ptr(), shown.data_ptr(), vis.data_ptr(), self._stream()))
             return cells, shown, vis
-        if self._encoded:
-            for g in self._groups:
-                N.check(self._lib.mg_encode_views(C.byref(g.cfg), C.byref(self._state), g.obs.data_ptr(), self._stream()))
-            return None
-        for g in self._groups:
-            N.check(self._lib.mg_render_obs(C.byref(g.cfg), C.byref(self._state), g.obs.data_ptr(), None, None,
-                                            None, self._stream()))
+        self._launch_views()
         return None
 
     def _pixel_buffer(self, g):
@@ -1469,13 +1436,11 @@ class MultiGridEnv(object):
 
     def _pixel_views(self):
         """rasterise every group's pixel views of the current state (render()'s side columns) -> {group: tensor}"""
-        if not self._encoded:
+        if self._encoded:
+            self._launch_views(pixels=True)
+        else:
             self._render()
-            return {id(g): g.obs for g in self._groups}
-        for g in self._groups:
-            N.check(self._lib.mg_render_obs(C.byref(g.cfg), C.byref(self._state), self._pixel_buffer(g).data_ptr(), None, None,
-                                            None, self._stream()))
-        return {id(g): g.pix for g in self._groups}
+        return {id(g): self._pixel_buffer(g) for g in self._groups}
 
     @_on_device
     def gen_obs(self):

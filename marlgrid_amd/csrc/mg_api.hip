@@ -66,6 +66,21 @@ int check_episode(const MgEpisode* ep, const MgGenProgram* auto_reset) {
     return MG_OK;
 }
 
+// what every step entry point checks, in the order a caller can observe: the episode block first (answered without a valid
+// config or a device), the config and the state, the buffers, the reset program.  `single_group`: the call steps AND writes
+// every agent's observation in one launch — view groups (n_view != 0) take mg_step + one launch per group instead.
+int check_step_args(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, const float* rewards,
+                    const MgGenProgram* auto_reset, const MgEpisode* ep, bool single_group) {
+    int e = check_episode(ep, auto_reset);
+    if (e) return e;
+    e = check_both(cfg, st);
+    if (e) return e;
+    if (!actions || !rewards) return MG_E_ARG;
+    if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return MG_E_ARG;
+    if (single_group && cfg->n_view != 0) return MG_E_ARG;
+    return auto_reset ? check_prog(cfg, auto_reset) : MG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -132,24 +147,14 @@ int32_t mg_episode_struct_size(void) { return (int32_t)sizeof(MgEpisode); }
 
 int32_t mg_step_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
                    const MgGenProgram* auto_reset, const MgEpisode* ep, void* stream) {
-    int e = check_episode(ep, auto_reset);      // (first: answered without a valid config or a device)
+    const int e = check_step_args(cfg, st, actions, action_bytes, rewards, auto_reset, ep, false);
     if (e) return e;
-    e = check_both(cfg, st);
-    if (e) return e;
-    if (!actions || !rewards) return MG_E_ARG;
-    if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return MG_E_ARG;
-    if (auto_reset && (e = check_prog(cfg, auto_reset))) return e;
     return rc(mg::launch_step(*cfg, *st, actions, action_bytes, rewards, auto_reset, (hipStream_t)stream, ep));
 }
 
 int32_t mg_step(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
                 const MgGenProgram* auto_reset, void* stream) {
-    int e = check_both(cfg, st);
-    if (e) return e;
-    if (!actions || !rewards) return MG_E_ARG;
-    if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return MG_E_ARG;
-    if (auto_reset && (e = check_prog(cfg, auto_reset))) return e;
-    return rc(mg::launch_step(*cfg, *st, actions, action_bytes, rewards, auto_reset, (hipStream_t)stream));
+    return mg_step_ep(cfg, st, actions, action_bytes, rewards, auto_reset, nullptr, stream);
 }
 
 int32_t mg_render_obs(const MgConfig* cfg, const MgState* st, uint8_t* obs, uint8_t* view_cells,
@@ -163,31 +168,24 @@ int32_t mg_render_obs(const MgConfig* cfg, const MgState* st, uint8_t* obs, uint
 static int32_t step_render(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
                            const MgGenProgram* auto_reset, uint8_t* obs, uint8_t* encode_out, void* stream,
                            const MgEpisode* ep = nullptr) {
-    int e = check_episode(ep, auto_reset);
+    const int e = check_step_args(cfg, st, actions, action_bytes, rewards, auto_reset, ep, true);
     if (e) return e;
-    e = check_both(cfg, st);
-    if (e) return e;
-    if (!actions || !rewards || !obs) return MG_E_ARG;
-    if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return MG_E_ARG;
-    if (cfg->n_view != 0) return MG_E_ARG;   // one launch steps AND renders every agent: view groups take mg_step + mg_render_obs
-    if (auto_reset && (e = check_prog(cfg, auto_reset))) return e;
-    if (encode_out && !mg::render_can_encode(*cfg)) return MG_E_UNSUPPORTED;
-    if (ep && !mg::render_can_episode(*cfg)) return MG_E_UNSUPPORTED;
-    mg::FusedStep fs;
+    if (!obs) return MG_E_ARG;      // (every check between the state's and this one answers MG_E_ARG too)
+    mg::RenderPick pick;
+    if ((encode_out || ep) && !mg::render_pick(*cfg, ep ? mg::kEpisode : mg::kEncode, &pick)) return MG_E_UNSUPPORTED;
+    mg::FusedStep fs{};
     fs.actions = actions;
     fs.rewards = rewards;
     fs.action_bytes = action_bytes;
     fs.enabled = 1;
     fs.has_prog = auto_reset ? 1 : 0;
     if (auto_reset) fs.prog = *auto_reset;
-    else { fs.prog.template_grid = nullptr; fs.prog.n_ops = 0; fs.prog.ops = nullptr; fs.prog.reject = nullptr; fs.prog.n_reject = 0; }
     fs.encode_out = encode_out;
     const uint32_t cells = (uint32_t)(cfg->W * cfg->H), n = (uint32_t)cfg->n_agents;
     fs.enc_m_cells = (uint32_t)((0x100000000ull + cells - 1) / cells);
     fs.enc_m_n = (uint32_t)((0x100000000ull + n - 1) / n);
-    fs.enc_ne = 0;        // (launch_render fills it in for the instantiations that use it)
     fs.has_ep = ep ? 1 : 0;
-    fs.ep = ep ? *ep : MgEpisode{};
+    if (ep) fs.ep = *ep;
     return rc(mg::launch_render(*cfg, *st, obs, nullptr, nullptr, nullptr, (hipStream_t)stream, &fs));
 }
 
@@ -223,29 +221,18 @@ int32_t mg_encode_views(const MgConfig* cfg, const MgState* st, uint8_t* views, 
     return rc(mg::launch_encode_views(*cfg, *st, views, (hipStream_t)stream));
 }
 
-int32_t mg_step_encode_views(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
-                             const MgGenProgram* auto_reset, uint8_t* views, void* stream) {
-    int e = check_both(cfg, st);
-    if (e) return e;
-    if (!actions || !rewards || !views) return MG_E_ARG;
-    if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return MG_E_ARG;
-    if (cfg->n_view != 0) return MG_E_ARG;   // as mg_step_render: view groups take mg_step + mg_encode_views per group
-    if (auto_reset && (e = check_prog(cfg, auto_reset))) return e;
-    return rc(mg::launch_step_encode_views(*cfg, *st, actions, action_bytes, rewards, auto_reset, views, (hipStream_t)stream));
-}
-
 int32_t mg_step_encode_views_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes,
                                 float* rewards, const MgGenProgram* auto_reset, uint8_t* views, const MgEpisode* ep,
                                 void* stream) {
-    int e = check_episode(ep, auto_reset);
+    const int e = check_step_args(cfg, st, actions, action_bytes, rewards, auto_reset, ep, true);
     if (e) return e;
-    e = check_both(cfg, st);
-    if (e) return e;
-    if (!actions || !rewards || !views) return MG_E_ARG;
-    if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return MG_E_ARG;
-    if (cfg->n_view != 0) return MG_E_ARG;   // as mg_step_encode_views
-    if (auto_reset && (e = check_prog(cfg, auto_reset))) return e;
+    if (!views) return MG_E_ARG;
     return rc(mg::launch_step_encode_views(*cfg, *st, actions, action_bytes, rewards, auto_reset, views, (hipStream_t)stream, ep));
+}
+
+int32_t mg_step_encode_views(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
+                             const MgGenProgram* auto_reset, uint8_t* views, void* stream) {
+    return mg_step_encode_views_ep(cfg, st, actions, action_bytes, rewards, auto_reset, views, nullptr, stream);
 }
 
 int32_t mg_put_obj(const MgConfig* cfg, const MgState* st, int32_t obj, int32_t x, int32_t y,
@@ -297,10 +284,8 @@ int32_t mg_render_kernel_name(const MgConfig* cfg, char* out, int32_t cap) {
     if (!cfg || !out || cap < 1 || cfg->B < 1 || cfg->n_agents < 1 || cfg->n_agents > MG_MAX_AGENTS || cfg->view_size < 1 ||
         cfg->view_size > MG_MAX_VIEW || cfg->tile_size < 1 || cfg->tile_size > 64 || cfg->cells_stride < 0 || cfg->n_tiles < 0)
         return MG_E_ARG;
-    mg::RenderPick pick = {0, 0, 0, 0, 0, 0};
-    MgState none = {};
-    const hipError_t e = mg::launch_render(*cfg, none, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &pick);
-    if (e != hipSuccess) { out[0] = 0; return MG_E_LAUNCH; }      // (the configuration does not fit LDS: mg_render_obs_lds_bytes)
+    mg::RenderPick pick;
+    if (!mg::render_pick(*cfg, mg::kPlain, &pick)) { out[0] = 0; return MG_E_LAUNCH; }      // (the configuration does not fit LDS: mg_render_obs_lds_bytes)
     snprintf(out, (size_t)cap, "mg::render_kernel<%d, %d, %d, %d, %d>", pick.vs, pick.ts, pick.wpb, pick.v, pick.rm);
     return (pick.vs == 0 ? 1 : 0) | (pick.ts == 0 ? 2 : 0);
 }

@@ -12,15 +12,9 @@ hipError_t launch_reset(const MgConfig& cfg, const MgState& st, const MgGenProgr
 hipError_t launch_step(const MgConfig& cfg, const MgState& st, const void* actions, int action_bytes,
                        float* rewards, const MgGenProgram* auto_reset, hipStream_t s, const MgEpisode* ep = nullptr);
 struct FusedStep;
-// which instantiation of mg::render_kernel<VS, TS, WPB, V, RM> a configuration gets (0 = the value is read from the
-// config at run time) and the LDS bytes of one of its workgroups: filled in INSTEAD of launching when handed to launch_render
-struct RenderPick { int vs, ts, wpb, v, rm, lds; };
+// (which instantiation a configuration gets, whether it has one with the encode / the episode code, its LDS: mg_render_pick.h)
 hipError_t launch_render(const MgConfig& cfg, const MgState& st, uint8_t* obs, uint8_t* view_cells,
-                         uint8_t* view_agent, uint8_t* vis_mask, hipStream_t s, const FusedStep* fused_step = nullptr,
-                         RenderPick* pick = nullptr);
-int render_min_lds_bytes(const MgConfig& cfg);
-bool render_can_episode(const MgConfig& cfg);     // mg_step_render_ep: this configuration has a step launch with the episode outputs
-bool render_can_encode(const MgConfig& cfg);      // mg_step_render_encode: this configuration's step launch can write the encoding too
+                         uint8_t* view_agent, uint8_t* vis_mask, hipStream_t s, const FusedStep* fused_step = nullptr);
 hipError_t launch_encode(const MgConfig& cfg, const MgState& st, const uint8_t* vis_mask, uint8_t* out,
                          hipStream_t s);
 // every agent's gen_obs_grid -> encode (mg_encode_views.hip): out uint8 [B][nv][vs][vs][3]

@@ -1379,24 +1379,15 @@ inline int device_cus() {
     return cached[dev];
 }
 
+// One launch of instantiation <VS_, TS_, WPB, VX_, RM_>; `lds`: its workgroup's dynamic LDS (render_lds_bytes — the launcher's pick)
 template <int VS_, int TS_, int WPB, int VX_ = 0, int RM_ = 0>
 hipError_t launch_render_t(const MgConfig& cfg, const MgState& st, uint8_t* obs, uint8_t* c, uint8_t* a,
-                                  uint8_t* v, hipStream_t s, const FusedStep* fs, RenderPick* pick) {
+                                  uint8_t* v, hipStream_t s, const FusedStep& fs, size_t lds) {
     static_assert(RM_ == 1 || TS_ == 0 || (TS_ % 8) != 0 || TS_ == 8 || TS_ == 16 || TS_ == 32, "see render_chunk_raster");
     const RenderScratch L = render_scratch_for(cfg, WPB, RM_);
     constexpr int V_ = VX_ & 15;
     const size_t atlas_lds = (V_ == 8 || V_ == 12) ? 0 : (size_t)render_atlas_lds_bytes(cfg, RM_);
     const RenderShared sh = render_shared_layout(cfg);
-    // (mg_step_render_encode: its table — fs->enc_ne dwords — lies behind the block-shared tables, the waves' scratch behind it)
-    constexpr bool kEnc = (VX_ & 16) != 0;
-    if (kEnc && (!fs || fs->enc_ne <= 0)) return hipErrorInvalidValue;
-    const size_t enc_lds = kEnc ? (size_t)fs->enc_ne * 4 : 0;
-    size_t lds = atlas_lds + sh.total + enc_lds + WPB * (size_t)L.total;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    if (pick) {     // mg_render_kernel_name: which instantiation this configuration gets — nothing is launched
-        pick->vs = VS_; pick->ts = TS_; pick->wpb = WPB; pick->v = VX_; pick->rm = RM_; pick->lds = (int)lds;
-        return hipSuccess;
-    }
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&render_kernel<VS_, TS_, WPB, VX_, RM_>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1440,66 +1431,16 @@ hipError_t launch_render_t(const MgConfig& cfg, const MgState& st, uint8_t* obs,
     if (const char* f = getenv("MG_RENDER_DEPTH")) lc.depth_mode = atoi(f);   // 1: every wave view -> raster env by env
 #endif
     hipLaunchKernelGGL((render_kernel<VS_, TS_, WPB, VX_, RM_>), dim3(blocks), dim3(WPB * 64), lds, s, cfg, st, obs, c, a, v,
-                       lc, *fs);
+                       lc, fs);
     return hipGetLastError();
 }
 
-// The instantiations, in groups: one translation unit per group (mg_render_inst_<g>.hip) makes them — in parallel —,
-// the dispatcher (mg_render.hip) only refers to them.  MG_RENDER_GROUP_x(X): X(VS, TS, WPB, V, RM).
-#define MG_RENDER_GROUP_A(X) /* the chunk raster at tile 8 */                                                              \
-    X(7, 8, 16, 0, 0) X(7, 8, 4, 0, 0) X(9, 8, 16, 0, 0) X(9, 8, 4, 0, 0) X(5, 8, 16, 0, 0) X(5, 8, 4, 0, 0)   \
-    X(3, 8, 16, 0, 0) X(3, 8, 4, 0, 0) X(0, 8, 8, 0, 0) X(0, 8, 4, 0, 0)
-#define MG_RENDER_GROUP_B(X) /* tile 16 / 32, the atlas in global memory */                                                \
-    X(7, 16, 16, 0, 0) X(7, 16, 4, 0, 0) X(7, 32, 16, 0, 0) X(7, 32, 4, 0, 0) X(0, 16, 8, 0, 0) X(0, 16, 4, 0, 0)               \
-    X(0, 32, 8, 0, 0) X(0, 32, 4, 0, 0) X(0, 8, 4, 8, 0) X(0, 16, 4, 8, 0) X(0, 32, 4, 8, 0) X(0, 0, 4, 8, 0) X(0, 0, 4, 8, 3)
-#define MG_RENDER_GROUP_C(X) /* assemble-and-stream: any other tile size */                                                \
-    X(7, 0, 16, 0, 0) X(7, 0, 4, 0, 0) X(0, 0, 8, 0, 0) X(0, 0, 4, 0, 0)
-#define MG_RENDER_GROUP_D(X) /* 'prestige': per-env recoloured tiles */                                                     \
-    X(7, 8, 12, 9, 0) X(7, 8, 8, 9, 0) X(7, 8, 4, 9, 0)                                                                       \
-    X(0, 8, 4, 9, 0) X(0, 16, 4, 9, 0)
-#define MG_RENDER_GROUP_E(X)                                                                                               \
-    X(7, 0, 12, 9, 0) X(7, 0, 8, 9, 0) X(7, 0, 4, 9, 0) X(0, 32, 4, 9, 0) X(0, 0, 4, 9, 0)                                      \
-    X(0, 8, 4, 12, 0) X(0, 16, 4, 12, 0) X(0, 32, 4, 12, 0) X(0, 0, 4, 12, 0) X(0, 0, 4, 12, 3)
-#if defined(MG_EXP) && (MG_EXP & 8)
-#define MG_RENDER_GROUP_X(X) X(7, 8, 12, 0, 0)      /* experiment builds only (mg_render.hip) */
-#else
-#define MG_RENDER_GROUP_X(X)
-#endif
-#define MG_RENDER_GROUP_G(X) /* the gather raster (mg_gather.h): view 7, 5- and 6-pixel tiles */                          \
-    X(7, 5, 16, 0, 2) X(7, 5, 4, 0, 2) X(7, 6, 16, 0, 2) X(7, 6, 4, 0, 2)
-#define MG_RENDER_GROUP_H(X) /* ... 7-, 9- and 10-pixel tiles */                                                           \
-    X(7, 7, 16, 0, 2) X(7, 7, 4, 0, 2) X(7, 9, 16, 0, 2) X(7, 9, 4, 0, 2) X(7, 10, 16, 0, 2) X(7, 10, 4, 0, 2)
-#define MG_RENDER_GROUP_M(X) /* the gather raster for views 11, 13, 15 at 5-pixel tiles (8-wave workgroups) */                  \
-    X(11, 5, 8, 0, 2) X(11, 5, 4, 0, 2) X(13, 5, 8, 0, 2) X(13, 5, 4, 0, 2) X(15, 5, 8, 0, 2) X(15, 5, 4, 0, 2)
-#define MG_RENDER_GROUP_L(X) /* assemble-and-stream with a compile-time view: views 3 .. 9 at any tile size */                    \
-    X(3, 0, 16, 0, 0) X(3, 0, 4, 0, 0) X(4, 0, 16, 0, 0) X(4, 0, 4, 0, 0) X(5, 0, 16, 0, 0) X(5, 0, 4, 0, 0)                       \
-    X(6, 0, 16, 0, 0) X(6, 0, 4, 0, 0) X(8, 0, 16, 0, 0) X(8, 0, 4, 0, 0) X(9, 0, 16, 0, 0) X(9, 0, 4, 0, 0)
-#define MG_RENDER_GROUP_K(X) /* the chunk raster at tile 8 for even views; the gather raster with 'prestige' agents at tile 5 */ \
-    X(4, 8, 16, 0, 0) X(4, 8, 4, 0, 0) X(6, 8, 16, 0, 0) X(6, 8, 4, 0, 0) X(8, 8, 16, 0, 0) X(8, 8, 4, 0, 0)                       \
-    X(7, 5, 12, 9, 2) X(7, 5, 8, 9, 2) X(7, 5, 4, 9, 2)
-#define MG_RENDER_GROUP_J(X) /* ... views 3, 4, 5, 6, 8, 9 at 5-pixel tiles */                                                       \
-    X(3, 5, 16, 0, 2) X(3, 5, 4, 0, 2) X(5, 5, 16, 0, 2) X(5, 5, 4, 0, 2) X(9, 5, 16, 0, 2) X(9, 5, 4, 0, 2)                       \
-    X(4, 5, 16, 0, 2) X(4, 5, 4, 0, 2) X(6, 5, 16, 0, 2) X(6, 5, 4, 0, 2) X(8, 5, 16, 0, 2) X(8, 5, 4, 0, 2)
-#define MG_RENDER_GROUP_I(X) /* ... 11- and 12-pixel tiles; 11 with 'prestige' agents (examples/human_player.py) */        \
-    X(7, 11, 16, 0, 2) X(7, 11, 4, 0, 2) X(7, 12, 16, 0, 2) X(7, 12, 4, 0, 2) X(7, 11, 12, 9, 2) X(7, 11, 8, 9, 2) X(7, 11, 4, 9, 2)
-#if defined(MG_AB_VARIANTS)
-#define MG_RENDER_GROUP_V(X) /* measurement variants (tools/ab_render.py) */                                               \
-    X(7, 8, 16, 2, 0) X(7, 8, 4, 2, 0) X(7, 8, 16, 3, 0) X(7, 8, 4, 3, 0) X(7, 8, 16, 4, 0) X(7, 8, 4, 4, 0)                     \
-    X(7, 8, 16, 6, 0) X(7, 8, 4, 6, 0) X(7, 8, 16, 11, 0) X(7, 8, 4, 11, 0) X(7, 8, 16, 0, 1) X(7, 8, 4, 0, 1)
-#else
-#define MG_RENDER_GROUP_V(X)
-#endif
-#define MG_RENDER_GROUP_N(X) /* mg_step_render_encode (V + 16): the BASELINE configs' shapes, the default tile, any view at tile 8 */ \
-    X(7, 8, 16, 16, 0) X(7, 8, 4, 16, 0) X(9, 8, 16, 16, 0) X(9, 8, 4, 16, 0) X(0, 8, 8, 16, 0) X(0, 8, 4, 16, 0)                       \
-    X(7, 5, 16, 16, 2) X(7, 5, 4, 16, 2)
-#define MG_RENDER_GROUP_P(X) /* mg_step_render_ep (V + 32): the shapes of group N */                                       \
-    X(7, 8, 16, 32, 0) X(7, 8, 4, 32, 0) X(9, 8, 16, 32, 0) X(9, 8, 4, 32, 0) X(0, 8, 8, 32, 0) X(0, 8, 4, 32, 0)                       \
-    X(7, 5, 16, 32, 2) X(7, 5, 4, 32, 2)
+// (the list of instantiations, MG_RENDER_ALL and its groups: mg_render_pick.h, next to the rules that pick from it)
 #define MG_RENDER_EXTERN(VS, TS, WPB, V, RM)                                                                               \
     extern template hipError_t launch_render_t<VS, TS, WPB, V, RM>(const MgConfig&, const MgState&, uint8_t*, uint8_t*,     \
-                                                                 uint8_t*, uint8_t*, hipStream_t, const FusedStep*, RenderPick*);
+                                                                 uint8_t*, uint8_t*, hipStream_t, const FusedStep&, size_t);
 #define MG_RENDER_INSTANTIATE(VS, TS, WPB, V, RM)                                                                          \
     template hipError_t launch_render_t<VS, TS, WPB, V, RM>(const MgConfig&, const MgState&, uint8_t*, uint8_t*, uint8_t*,  \
-                                                          uint8_t*, hipStream_t, const FusedStep*, RenderPick*);
+                                                          uint8_t*, hipStream_t, const FusedStep&, size_t);
 
 }  // namespace mg

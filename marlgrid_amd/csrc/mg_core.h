@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "marlgrid_hip.h"
+#include "mg_step_layout.h"
 
 #if defined(__HIPCC__)
 #define MG_HD __host__ __device__ __forceinline__
@@ -55,6 +56,28 @@ MG_HD void record_error(const MgState& st, int b, int err) {
 // forward vector per dir: agents.py:183  [(1,0),(0,1),(-1,0),(0,-1)]
 MG_HD int dir_dx(int d) { return d == 0 ? 1 : (d == 2 ? -1 : 0); }
 MG_HD int dir_dy(int d) { return d == 1 ? 1 : (d == 3 ? -1 : 0); }
+
+// ---- the view map ---------------------------------------------------------------
+// An agent at (x, y) heading `dir` sees a vs x vs window, `off` rows of it behind the agent, rotated so that it looks up.
+// The four headings folded into an origin, a swap bit and two signs: view cell (column va, row vb) is the world cell
+//   p = swap ? vb : va, q = swap ? va : vb;  wx = x0 +- p;  wy = y0 +- q
+// view_map packs them: x0 + 256 | (y0 + 256) << 10 | swap << 20 | negx << 21 | negy << 22.
+MG_HD uint32_t view_map(int x, int y, int dir, int vs, int off) {
+    const int h = vs / 2;
+    int x0, y0;
+    uint32_t bits;
+    if (dir == 3)      { x0 = x - h;                 y0 = y - (vs - 1) + off;  bits = 0u; }
+    else if (dir == 0) { x0 = x - off + (vs - 1);    y0 = y - h;               bits = 1u | 2u; }
+    else if (dir == 1) { x0 = x - h + (vs - 1);      y0 = y - off + (vs - 1);  bits = 2u | 4u; }
+    else               { x0 = x - vs + 1 + off;      y0 = y - h + (vs - 1);    bits = 1u | 4u; }
+    return (uint32_t)(x0 + 256) | ((uint32_t)(y0 + 256) << 10) | (bits << 20);
+}
+MG_HD void view_world(uint32_t word0, int va, int vb, int* wx, int* wy) {
+    const bool swap = (word0 >> 20) & 1u;
+    const int p = swap ? vb : va, q = swap ? va : vb;
+    *wx = (int)(word0 & 0x3FFu) - 256 + (((word0 >> 21) & 1u) ? -p : p);
+    *wy = (int)((word0 >> 10) & 0x3FFu) - 256 + (((word0 >> 22) & 1u) ? -q : q);
+}
 
 // ---- per-env MT19937: lazy regeneration + a look-ahead head ------------------------------------
 // numpy's RandomState regenerates all 624 words when a block is exhausted.  The same sequence
@@ -520,6 +543,76 @@ struct StepScratch {        // per-workgroup arrays, this env is column `col`, e
     unsigned long long* stamp = nullptr;   // measurement build: 5 words, wall_clock64 at the section ends of step_run (or null)
 #endif
 };
+// The scratch of column `col` carved from a workgroup's LDS (mg_step_layout.h).  Lane per env: `base` 16-byte aligned,
+// lane_step_bytes(n, S) bytes; the object table and the flags inside it are filled by stage_obj_tables.
+MG_HD StepScratch lane_step_scratch(uint8_t* base, int n, int S, int col) {
+    const LaneStepLayout l = lane_step_layout(n, S);
+    StepScratch sc;
+    sc.rec = reinterpret_cast<uint64_t*>(base + l.rec);
+    sc.head = reinterpret_cast<uint32_t*>(base + l.head);
+    sc.act = base + l.act;
+    sc.fb = base + l.fb;
+    sc.ord = base + l.ord;
+    sc.obj = reinterpret_cast<const MgObjDesc*>(base + l.obj);
+    sc.oflags = base + l.oflags;
+    sc.S = S;
+    sc.col = col;
+    return sc;
+}
+// ... and the obs kernel's fused step: `base` 8-byte aligned, fused_step_bytes(n) bytes, the tables the workgroup's own
+MG_HD StepScratch fused_step_scratch(uint8_t* base, int n, int col, const MgObjDesc* obj, const uint8_t* oflags) {
+    const FusedStepLayout l = fused_step_layout(n);
+    StepScratch sc;
+    sc.rec = reinterpret_cast<uint64_t*>(base + l.rec);
+    sc.head = reinterpret_cast<uint32_t*>(base + l.head);
+    sc.act = base + l.act;
+    sc.pflag = base + l.pflag;                  // step_par_*: moved / needs the loop
+    sc.ordp = base + l.ordp;                    // ... the agent's turn
+    sc.ord = sc.ordp;                           // (more than 16 agents — no lane-parallel resolution —: iter_order)
+    sc.psc = reinterpret_cast<int32_t*>(base + l.psc);   // ... the env's step count
+    sc.rec_out = sc.rec;                        // (in place: the lanes of a wave run in lockstep)
+    sc.fb = nullptr;                            // (the grid is a staged LDS copy: no pre-load)
+    sc.obj = obj;
+    sc.oflags = oflags;
+    sc.S = 8;
+    sc.col = col;
+    return sc;
+}
+// The shared tables of a workgroup of T threads, thread `tid`'s part (a barrier follows): the object table in 16-byte
+// pieces (s_obj 16-byte aligned; null: the caller reads the flags alone — reset, placement) and every kind's flags, id 0 =
+// None and the ids past n_obj as zero.
+MG_HD void stage_obj_tables(const MgConfig& cfg, MgObjDesc* s_obj, uint8_t* s_oflags, int tid, int T) {
+    typedef struct { uint32_t v[4]; } __attribute__((aligned(16))) q16;
+    static_assert(sizeof(MgObjDesc) == 2 * sizeof(q16), "an object descriptor is two 16-byte pieces");
+    if (s_obj) {
+        const q16* src = reinterpret_cast<const q16*>(cfg.obj);
+        q16* dst = reinterpret_cast<q16*>(s_obj);
+        for (int i = tid; i < cfg.n_obj * 2; i += T) dst[i] = src[i];
+    }
+    for (int i = tid; i < MG_MAX_OBJ; i += T) s_oflags[i] = (i > 0 && i < cfg.n_obj) ? cfg.obj[i].flags : 0;
+}
+// the arguments of a step launch, as step_kernel and encode_views_kernel take them
+struct StepArgs {
+    const void* actions;    // [B][n] little-endian integers of `action_bytes` (1, 4 or 8) bytes each
+    float* rewards;         // [B][n]
+    int32_t action_bytes, has_prog, has_ep, reserved0;
+    MgGenProgram prog;      // auto-reset program (has_prog)
+    MgEpisode ep;           // the mg_*_ep entry points (has_ep)
+};
+// ... filled by the launchers; false: an action width that is not 1, 4 or 8 bytes (nothing is to be launched)
+inline bool step_args(StepArgs* a, const void* actions, int action_bytes, float* rewards, const MgGenProgram* prog,
+                      const MgEpisode* ep) {
+    if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return false;
+    *a = StepArgs{};
+    a->actions = actions;
+    a->action_bytes = action_bytes;
+    a->rewards = rewards;
+    a->has_prog = prog ? 1 : 0;
+    if (prog) a->prog = *prog;
+    a->has_ep = ep ? 1 : 0;
+    if (ep) a->ep = *ep;
+    return true;
+}
 struct StepEnv { int pos0, sc0; };
 // what step_run reports: whether it wrote the grid slice; with StepScratch::defer_writeback also where the RNG head
 // ring starts (mt_finish_ring) — the stepped records are in StepScratch::rec, the head in StepScratch::head

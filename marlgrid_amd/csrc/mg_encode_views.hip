@@ -38,19 +38,8 @@ constexpr int kEvTab = 256 * 4 * 2;          // triples + see_behind bit, hide_i
 // then encodes their views from the state it has just written (the same workgroup: visible after the barrier)
 struct EncViewsStep {
     MgState st;
-    MgGenProgram prog;
-    int32_t has_prog, action_bytes;
-    const void* actions;
-    float* rewards;
-    int32_t has_ep, reserved0;
-    MgEpisode ep;       // mg_step_encode_views_ep (has_ep)
+    StepArgs a;
 };
-
-// LDS of the step phase for E envs (step_kernel's layout with S = E)
-static size_t encode_views_step_lds(const MgConfig& cfg, int E) {
-    return (size_t)cfg.n_agents * E * 8 + MG_MAX_OBJ * sizeof(MgObjDesc) + (size_t)MG_MT_HEAD * E * 4 + 3 * (size_t)cfg.n_agents * E +
-           MG_MAX_OBJ;
-}
 
 template <int VS_, bool STEP_>
 __global__ __launch_bounds__(kBlock) void encode_views_kernel(MgConfig cfg, const uint8_t* __restrict__ grid,
@@ -61,37 +50,21 @@ __global__ __launch_bounds__(kBlock) void encode_views_kernel(MgConfig cfg, cons
     if constexpr (STEP_) {
         // 0. the step of envs b0 .. b0 + E - 1 (E = PB / nv), one lane each; its LDS is reused by the phases below
         const int E = lc.PB / lc.nv, n = cfg.n_agents;
-        uint64_t* s_mem = reinterpret_cast<uint64_t*>(smem);
-        StepScratch sc;
-        sc.rec = s_mem;                                                          // [n][E] u64
-        MgObjDesc* s_obj = reinterpret_cast<MgObjDesc*>(s_mem + (size_t)n * E);  // [MG_MAX_OBJ]
-        sc.head = reinterpret_cast<uint32_t*>(s_obj + MG_MAX_OBJ);               // [MG_MT_HEAD][E]
-        sc.act = reinterpret_cast<uint8_t*>(sc.head + MG_MT_HEAD * E);           // [n][E]
-        sc.fb = sc.act + (size_t)n * E;                                          // [n][E]
-        sc.ord = sc.fb + (size_t)n * E;                                          // [n][E]
-        uint8_t* s_oflags = sc.ord + (size_t)n * E;                              // [MG_MAX_OBJ]
-        sc.obj = s_obj;
-        sc.oflags = s_oflags;
-        sc.S = E;
-        sc.col = tid;
-        if (fs.has_ep) { sc.ep = &fs.ep; sc.ep_rewards = fs.rewards; }
+        StepScratch sc = lane_step_scratch(smem, n, E, tid);             // (step_kernel's layout with S = E)
+        if (fs.a.has_ep) { sc.ep = &fs.a.ep; sc.ep_rewards = fs.a.rewards; }
         const int b = blockIdx.x * E + tid;
         const bool live = tid < E && b < cfg.B;
-        {
-            const uint2* src = reinterpret_cast<const uint2*>(cfg.obj);      // (8-byte pieces: n * E records may be odd)
-            uint2* dst = reinterpret_cast<uint2*>(s_obj);
-            for (int i = tid; i < cfg.n_obj * 4; i += kBlock) dst[i] = src[i];
-            for (int i = tid; i < MG_MAX_OBJ; i += kBlock) s_oflags[i] = (i > 0 && i < cfg.n_obj) ? cfg.obj[i].flags : 0;
-        }
+        const LaneStepLayout l = lane_step_layout(n, E);
+        stage_obj_tables(cfg, reinterpret_cast<MgObjDesc*>(smem + l.obj), smem + l.oflags, tid, kBlock);
         StepEnv env{0, 0};
         __syncthreads();
-        if (live) env = step_load(cfg, fs.st, fs.actions, fs.action_bytes, b, sc);
+        if (live) env = step_load(cfg, fs.st, fs.a.actions, fs.a.action_bytes, b, sc);
         __syncthreads();
-        if (live) step_run(cfg, fs.st, fs.prog, fs.has_prog != 0, fs.rewards, b, env, sc, fs.st.grid + (size_t)b * cfg.cells_stride);
+        if (live) step_run(cfg, fs.st, fs.a.prog, fs.a.has_prog != 0, fs.a.rewards, b, env, sc, fs.st.grid + (size_t)b * cfg.cells_stride);
         __syncthreads();      // (the envs' new grids and records, written to global memory above, are read below)
     }
     const int VS = VS_ ? VS_ : cfg.view_size, VV = VS * VS, n = cfg.n_agents, nv = lc.nv, H = cfg.H, W = cfg.W;
-    const int off = cfg.view_offset, h = VS / 2;
+    const int off = cfg.view_offset;
     uint32_t* s_tab = reinterpret_cast<uint32_t*>(smem);                       // [256] type | colour << 8 | state << 16 | see << 24
     uint32_t* s_hide = s_tab + 256;                                            // [256] bit k: agent k hides this object id
     uint64_t* s_rec = reinterpret_cast<uint64_t*>(smem + kEvTab);              // [env_cap][n]
@@ -121,8 +94,7 @@ __global__ __launch_bounds__(kBlock) void encode_views_kernel(MgConfig cfg, cons
     for (int i = tid; i < ne * n; i += kBlock) s_rec[i] = agents[(size_t)b0 * n + i];
     __syncthreads();
 
-    // B. one lane per pair: the view as an affine map of (column va, row vb), p = swap ? vb : va, q = swap ? va : vb,
-    //    wx = x0 +- p, wy = y0 +- q — word 0: x0 + 256 | (y0 + 256) << 10 | swap << 20 | negx << 21 | negy << 22;
+    // B. one lane per pair: word 0 the view's map of (column va, row vb) to world cells (view_map, mg_core.h);
     //    word 1: viewer k | active << 8 | env slot << 16
     for (int t = tid; t < cnt; t += kBlock) {
         const long long p = p0 + t;
@@ -131,24 +103,14 @@ __global__ __launch_bounds__(kBlock) void encode_views_kernel(MgConfig cfg, cons
         const int slot = (int)(b - b0);
         const uint64_t r = s_rec[slot * n + k];
         const int x = (int)rec_byte(r, MG_AG_X), y = (int)rec_byte(r, MG_AG_Y), dir = (int)rec_byte(r, MG_AG_DIR);
-        int x0, y0;
-        uint32_t bits;
-        if (dir == 3)      { x0 = x - h;                 y0 = y - (VS - 1) + off;  bits = 0u; }
-        else if (dir == 0) { x0 = x - off + (VS - 1);    y0 = y - h;               bits = 1u | 2u; }
-        else if (dir == 1) { x0 = x - h + (VS - 1);      y0 = y - off + (VS - 1);  bits = 2u | 4u; }
-        else               { x0 = x - VS + 1 + off;      y0 = y - h + (VS - 1);    bits = 1u | 4u; }
         const uint32_t active = (rec_byte(r, MG_AG_FLAGS) & MG_AF_ACTIVE) ? 1u : 0u;
-        s_aff[t] = make_uint2((uint32_t)(x0 + 256) | ((uint32_t)(y0 + 256) << 10) | (bits << 20),
-                              (uint32_t)k | (active << 8) | ((uint32_t)slot << 16));
+        s_aff[t] = make_uint2(view_map(x, y, dir, VS, off), (uint32_t)k | (active << 8) | ((uint32_t)slot << 16));
     }
     __syncthreads();
 
     // the world cell of view cell (va, vb) of pair t, -1 outside the grid
     auto world_cell = [&](const uint2 aff, const int va, const int vb, int& wx, int& wy) -> int {
-        const bool swap = (aff.x >> 20) & 1u;
-        const int p = swap ? vb : va, q = swap ? va : vb;
-        wx = (int)(aff.x & 0x3FFu) - 256 + (((aff.x >> 21) & 1u) ? -p : p);
-        wy = (int)((aff.x >> 10) & 0x3FFu) - 256 + (((aff.x >> 22) & 1u) ? -q : q);
+        view_world(aff.x, va, vb, &wx, &wy);
         return ((unsigned)wx < (unsigned)W && (unsigned)wy < (unsigned)H) ? wx * H + wy : -1;
     };
 
@@ -278,28 +240,20 @@ hipError_t launch_encode_views(const MgConfig& cfg, const MgState& st, uint8_t* 
         if (fs) pb = PB / nv * nv;
         if (fs && pb == 0) return hipErrorNotSupported;
         lds = encode_views_lds(cfg, pb, nv, &lc.env_cap, &lc.stage_off);
-        if (fs) lds = std::max(lds, encode_views_step_lds(cfg, pb / nv));
+        if (fs) lds = std::max(lds, lane_step_bytes(cfg.n_agents, pb / nv));
         lc.PB = pb;
         if (lds <= 48 * 1024 || PB == 1) break;
     }
     if (lds > 64 * 1024) return fs ? hipErrorNotSupported : hipErrorInvalidValue;
     const unsigned blocks = (unsigned)((lc.pairs + lc.PB - 1) / lc.PB);
-    EncViewsStep none{};
-#define MG_EV_LAUNCH(V, F)                                                                                                \
-    hipLaunchKernelGGL((encode_views_kernel<V, F>), dim3(blocks), dim3(kBlock), lds, s, cfg, st.grid, st.agents, out, lc,   \
-                       fs ? *fs : none)
-    if (fs) {
-        if (VS == 7) MG_EV_LAUNCH(7, true);
-        else if (VS == 5) MG_EV_LAUNCH(5, true);
-        else if (VS == 9) MG_EV_LAUNCH(9, true);
-        else MG_EV_LAUNCH(0, true);
-    } else {
-        if (VS == 7) MG_EV_LAUNCH(7, false);
-        else if (VS == 5) MG_EV_LAUNCH(5, false);
-        else if (VS == 9) MG_EV_LAUNCH(9, false);
-        else MG_EV_LAUNCH(0, false);
-    }
-#undef MG_EV_LAUNCH
+    // the instantiation: the first of the compile-time view sizes that is this one, else the run-time view (0)
+    void (*kernel)(MgConfig, const uint8_t*, const uint64_t*, uint8_t*, EncViewsLaunch, EncViewsStep) = nullptr;
+#define MG_EV_VIEWS(X) X(7) X(5) X(9) X(0)
+#define MG_EV_PICK(V) if (!kernel && (V == 0 || VS == V)) kernel = fs ? encode_views_kernel<V, true> : encode_views_kernel<V, false>;
+    MG_EV_VIEWS(MG_EV_PICK)
+#undef MG_EV_PICK
+#undef MG_EV_VIEWS
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kBlock), lds, s, cfg, st.grid, st.agents, out, lc, fs ? *fs : EncViewsStep{});
     return hipGetLastError();
 }
 
@@ -307,13 +261,7 @@ hipError_t launch_step_encode_views(const MgConfig& cfg, const MgState& st, cons
                                     float* rewards, const MgGenProgram* prog, uint8_t* out, hipStream_t s, const MgEpisode* ep) {
     EncViewsStep fs{};
     fs.st = st;
-    fs.actions = actions;
-    fs.action_bytes = action_bytes;
-    fs.rewards = rewards;
-    fs.has_prog = prog ? 1 : 0;
-    if (prog) fs.prog = *prog;
-    fs.has_ep = ep ? 1 : 0;
-    if (ep) fs.ep = *ep;
+    if (!step_args(&fs.a, actions, action_bytes, rewards, prog, ep)) return hipErrorInvalidValue;
     const hipError_t e = launch_encode_views(cfg, st, out, s, &fs);
     if (e != hipErrorNotSupported) return e;
     // no workgroup of whole envs fits (many agents with a large view): the step, then the views

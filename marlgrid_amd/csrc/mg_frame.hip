@@ -63,13 +63,9 @@ __global__ __launch_bounds__(kBlock) void frame_kernel(MgConfig cfg, MgState st,
     __syncthreads();
     if (highlight) {
         // transparency rows of every agent's view (as in the obs kernel, phase 3)
-        const int h = VS / 2, off = cfg.view_offset;
+        const int off = cfg.view_offset;
         auto world = [&](const uint64_t r, int va, int vb, int& wx, int& wy) {
-            const int x = (int)rec_byte(r, MG_AG_X), y = (int)rec_byte(r, MG_AG_Y), dir = (int)rec_byte(r, MG_AG_DIR);
-            if (dir == 3)      { wx = x - h + va;              wy = y - (VS - 1) + off + vb; }
-            else if (dir == 0) { wx = x - off + (VS - 1 - vb); wy = y - h + va; }
-            else if (dir == 1) { wx = x - h + (VS - 1 - va);   wy = y - off + (VS - 1 - vb); }
-            else               { wx = x - VS + 1 + off + vb;   wy = y - h + (VS - 1 - va); }
+            view_world(view_map((int)rec_byte(r, MG_AG_X), (int)rec_byte(r, MG_AG_Y), (int)rec_byte(r, MG_AG_DIR), VS, off), va, vb, &wx, &wy);
         };
         for (int it = tid; it < n * VS * VS; it += kBlock) {
             const int k = it / (VS * VS), c = it - k * VS * VS, vb = c / VS, va = c - vb * VS;

@@ -140,8 +140,12 @@ __device__ __forceinline__ const T& kernarg_again(size_t offset) {
 // (Inlined: as a call, the by-value launch structs would be copied to per-lane scratch.  The 16-wave
 // workgroups run at the 128-VGPR limit; the few dwords the step's live ranges spill are spilled and
 // reloaded around this region, once per batch — checked in the ISA: no scratch access in the raster loops.)
-__device__ __forceinline__ StepScratch fused_step_scratch(const MgConfig& cfg, int lane, uint8_t* sp, const MgObjDesc* s_obj,
-                                                          const uint8_t* s_oflags) {
+// (fused_step_layout's columns — its byte count sizes this region in render_scratch_layout — in the kernel's own words,
+// a chain of pointers: formed from the layout's offsets, as mg::fused_step_scratch of mg_core.h forms them for the host
+// harness, the same addresses come out of other instructions and every instantiation is scheduled differently.  Nothing
+// on the host compiles THIS text: that it carves the same columns is held by the GPU tests of the fused step alone.)
+__device__ __forceinline__ StepScratch fused_step_scratch_lds(const MgConfig& cfg, int lane, uint8_t* sp, const MgObjDesc* s_obj,
+                                                              const uint8_t* s_oflags) {
     const int n = cfg.n_agents;
     StepScratch sc;
     sc.rec = reinterpret_cast<uint64_t*>(sp);                                   // [n][8]
@@ -500,7 +504,7 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                 }
             }
             StepScratch sc;
-            if (fs.enabled) sc = fused_step_scratch(cfg, lane, ws + L.step, s_obj, s_oflags);
+            if (fs.enabled) sc = fused_step_scratch_lds(cfg, lane, ws + L.step, s_obj, s_oflags);
             StepEnv se = {0, 0};
 #if defined(MG_AB_VARIANTS)
             sc.stamp = (d_ab_stamps && lane == 0) ? d_ab_stamps + (size_t)(blockIdx.x * WPB + wave) * 24 + (first ? 8 : 16) : nullptr;
@@ -814,7 +818,7 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
             const uint32_t k = s_vmap[v];
             const uint64_t r = g_rec[__mul24(g, rec_stride) + (int)k];
             const int x = (int)rec_byte(r, MG_AG_X), y = (int)rec_byte(r, MG_AG_Y), dir = (int)rec_byte(r, MG_AG_DIR);
-            int x0, y0;
+            int x0, y0;       // (mg::view_map's word 0, mg_core.h, in the kernel's own words: calling it reorders the instructions here)
             uint32_t bits;
             if (dir == 3)      { x0 = x - h;                 y0 = y - (VS - 1) + off;  bits = 0u; }
             else if (dir == 0) { x0 = x - off + (VS - 1);    y0 = y - h;               bits = 1u | 2u; }

@@ -8,13 +8,7 @@
 #include <stdint.h>
 
 #include "marlgrid_hip.h"
-
-// the layout functions: the kernels call them too
-#if defined(__HIPCC__)
-#define MG_LAYOUT_FN __host__ __device__ inline
-#else
-#define MG_LAYOUT_FN inline
-#endif
+#include "mg_step_layout.h"   // MG_LAYOUT_FN (the layout functions: the kernels call them too) and the fused step's columns
 
 namespace mg {
 
@@ -121,9 +115,8 @@ MG_LAYOUT_FN RenderScratch render_scratch_layout(int cells_stride, int n, int nv
     s.out = o;   o += round_up(out_bytes, 16);   // assemble-and-stream raster: the piece being assembled
     s.piece_rows = piece_rows;
     s.out_chunks = round_up(out_bytes, 16) / 16;
-    // fused step (mg_step_render): lane j < stage_envs steps staged env j; its [item][8] columns: records, RNG look-ahead,
-    // actions, the agent-parallel resolution's flags and turns (step_par_*, mg_core.h), the envs' step counts
-    s.step = o;  o += round_up(n * 8 * 8 + MG_MT_HEAD * 8 * 4 + 3 * n * 8 + 8 * 4, 16);
+    // fused step (mg_step_render): lane j < stage_envs steps staged env j; its [item][8] columns (fused_step_layout)
+    s.step = o;  o += round_up((int)fused_step_bytes(n), 16);
     s.total = o;
     return s;
 }

@@ -12,17 +12,20 @@
 
 namespace mg {
 
-// object flags -> LDS once per workgroup (the bodies test can_overlap per rejection-sampling draw)
-__device__ __forceinline__ void stage_oflags(const MgConfig& cfg, uint8_t* s_oflags) {
-    for (int i = threadIdx.x; i < MG_MAX_OBJ; i += kBlock) s_oflags[i] = (i > 0 && i < cfg.n_obj) ? cfg.obj[i].flags : 0;
+// object flags -> LDS once per workgroup (the bodies test can_overlap per rejection-sampling draw), behind the records:
+// reset_scratch_bytes (mg_step_layout.h)
+__device__ __forceinline__ uint8_t* stage_oflags(const MgConfig& cfg, uint64_t* s_rec) {
+    uint8_t* s_oflags = reinterpret_cast<uint8_t*>(s_rec + (size_t)cfg.n_agents * kBlock);
+    stage_obj_tables(cfg, nullptr, s_oflags, threadIdx.x, kBlock);
     __syncthreads();
+    return s_oflags;
 }
+static size_t reset_lds(const MgConfig& cfg) { return reset_scratch_bytes(cfg.n_agents, kBlock); }
 
 __global__ __launch_bounds__(kBlock) void reset_kernel(MgConfig cfg, MgState st, MgGenProgram prog,
                                                        const uint8_t* __restrict__ mask) {
     extern __shared__ __attribute__((aligned(16))) uint64_t s_rec[];  // [n][kBlock]
-    uint8_t* s_oflags = reinterpret_cast<uint8_t*>(s_rec + (size_t)cfg.n_agents * kBlock);
-    stage_oflags(cfg, s_oflags);
+    uint8_t* s_oflags = stage_oflags(cfg, s_rec);
     const int tid = threadIdx.x;
     const int b = blockIdx.x * kBlock + tid;
     if (b >= cfg.B) return;
@@ -54,8 +57,7 @@ __global__ __launch_bounds__(kBlock) void place_kernel(MgConfig cfg, MgState st,
                                                        const uint8_t* __restrict__ mask, const uint8_t* __restrict__ reject,
                                                        int32_t* __restrict__ out_pos, uint8_t* __restrict__ out_ok) {
     extern __shared__ __attribute__((aligned(16))) uint64_t s_rec[];  // [n][kBlock]
-    uint8_t* s_oflags = reinterpret_cast<uint8_t*>(s_rec + (size_t)cfg.n_agents * kBlock);
-    stage_oflags(cfg, s_oflags);
+    uint8_t* s_oflags = stage_oflags(cfg, s_rec);
     const int b = blockIdx.x * kBlock + threadIdx.x;
     if (b >= cfg.B) return;
     if (mask && !mask[b]) return;
@@ -67,8 +69,7 @@ hipError_t launch_place(const MgConfig& cfg, const MgState& st, int what, int x0
                         const int32_t* fixed_pos, const uint8_t* mask, const uint8_t* reject, int32_t* out_pos,
                         uint8_t* out_ok, hipStream_t s) {
     if (cfg.B <= 0) return hipSuccess;
-    const size_t lds = (size_t)cfg.n_agents * kBlock * sizeof(uint64_t) + MG_MAX_OBJ;
-    hipLaunchKernelGGL(place_kernel, dim3((cfg.B + kBlock - 1) / kBlock), dim3(kBlock), lds, s, cfg, st, what, x0, y0,
+    hipLaunchKernelGGL(place_kernel, dim3((cfg.B + kBlock - 1) / kBlock), dim3(kBlock), reset_lds(cfg), s, cfg, st, what, x0, y0,
                        x1, y1, max_tries, fixed_pos, mask, reject, out_pos, out_ok);
     return hipGetLastError();
 }
@@ -76,8 +77,7 @@ hipError_t launch_place(const MgConfig& cfg, const MgState& st, int what, int x0
 hipError_t launch_reset(const MgConfig& cfg, const MgState& st, const MgGenProgram& prog, const uint8_t* mask,
                         hipStream_t s) {
     if (cfg.B <= 0) return hipSuccess;
-    size_t lds = (size_t)cfg.n_agents * kBlock * sizeof(uint64_t) + MG_MAX_OBJ;
-    hipLaunchKernelGGL(reset_kernel, dim3((cfg.B + kBlock - 1) / kBlock), dim3(kBlock), lds, s, cfg, st, prog, mask);
+    hipLaunchKernelGGL(reset_kernel, dim3((cfg.B + kBlock - 1) / kBlock), dim3(kBlock), reset_lds(cfg), s, cfg, st, prog, mask);
     return hipGetLastError();
 }
 

@@ -371,6 +371,21 @@ def gen_frames_big(out):
     np.savez_compressed(out, **d)
 
 
+def gen_frame_view31(out):
+    """ONE highlighted frame of the largest view (31 x 31: the frame kernel's shadow cast walks its rows in memory), whole:
+    `MultiGridEnv.render(mode='rgb_array', tile_size=8, show_agent_views=False)` of Limit-3AgentCluttered33x33-view31-tile4
+    after 6 steps."""
+    name, seed, steps, ts = "Limit-3AgentCluttered33x33-view31-tile4", 1337, 6, 8
+    spec = scenarios.registered(name)
+    env = refstate.make_ref_env(spec, scenarios.ref_recipe(name), seed=seed)
+    env.reset()
+    acts = np.random.RandomState(seed).choice(3, size=(steps, len(spec["agents"]))).astype(np.int8)
+    for t in range(steps):
+        env.step(acts[t])
+    img = np.asarray(env.render(mode="rgb_array", tile_size=ts, show_agent_views=False)).astype(np.uint8)
+    np.savez_compressed(out, name=np.array(name), seed=np.array(seed), tile_size=np.array(ts), actions=acts, full=img)
+
+
 def gen_interact(m, out):
     """Hand-built pickup/drop/toggle scenes (base.py:587-617 — 'TODO: verify' in the reference).
     Each scene: EmptyMultiGrid 7x7, 2 agents teleported via a fresh grid + put_obj; scripted
@@ -539,6 +554,8 @@ def main():
         gen_frames(os.path.join(HERE, "frames.npz"))
     if "frames" in which or "frames_big" in which:
         gen_frames_big(os.path.join(HERE, "frames_big.npz"))
+    if "frames" in which or "frame_view31" in which:
+        gen_frame_view31(os.path.join(HERE, "frame_view31.npz"))
     if "interact" in which:
         gen_interact(m, os.path.join(HERE, "interact.npz"))
     if "live" in which:

@@ -113,13 +113,15 @@ class HostEmu(object):
     def _reset_with(self, trace, mask):
         self._last_prog = prog = self._prog(trace)
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
-        self.L.emu_reset(C.byref(self._cfg()), C.byref(self.state), C.byref(prog), None if m is None else _ptr(m))
+        rc = self.L.emu_reset(C.byref(self._cfg()), C.byref(self.state), C.byref(prog), None if m is None else _ptr(m))
+        assert rc == 0, rc
 
     def reset(self, env_mask=None):
         self.env.reset()                                # re-records `_gen_grid` (dry: nothing else)
         self._reset_with(self.env._dry_trace, env_mask)
 
-    def step(self, actions):
+    def _step(self, actions, ep=None):
+        """one emulated step launch; ep: a byref'd _native.Episode (hostemu_episode.EpisodeEmu) or None"""
         a = np.ascontiguousarray(actions, np.int64).reshape(self.B, self.n)
         prog = None
         if self.auto_reset:
@@ -127,11 +129,14 @@ class HostEmu(object):
             self._last_prog = self._prog(self.env._dry_trace)
             prog = C.byref(self._last_prog)
         if self.par:
-            rc = self.L.emu_step_par(C.byref(self._cfg()), C.byref(self.state), _ptr(a), 8, _ptr(self.rewards), prog,
+            rc = self.L.emu_step_par(C.byref(self._cfg()), C.byref(self.state), _ptr(a), 8, _ptr(self.rewards), prog, ep,
                                      C.byref(self.n_serial))
         else:
-            rc = self.L.emu_step(C.byref(self._cfg()), C.byref(self.state), _ptr(a), 8, _ptr(self.rewards), prog)
+            rc = self.L.emu_step(C.byref(self._cfg()), C.byref(self.state), _ptr(a), 8, _ptr(self.rewards), prog, ep)
         assert rc == 0, rc
+
+    def step(self, actions):
+        self._step(actions)
         return self.rewards.copy(), self.done.astype(bool)
 
     def place(self, what, region, max_tries=100000, fixed_pos=None, mask=None, reject=None):
@@ -144,9 +149,10 @@ class HostEmu(object):
         if reject is not None:                           # (W, H) table
             rj = np.zeros(self.env.cells_stride, np.uint8)
             rj[:self.env.width * self.env.height] = np.asarray(reject, np.uint8).reshape(-1)
-        self.L.emu_place(C.byref(self._cfg()), C.byref(self.state), what, x0, y0, x1, y1, int(max_tries),
-                         None if fp is None else _ptr(fp), None if m is None else _ptr(m),
-                         None if rj is None else _ptr(rj), _ptr(pos), _ptr(ok))
+        rc = self.L.emu_place(C.byref(self._cfg()), C.byref(self.state), what, x0, y0, x1, y1, int(max_tries),
+                              None if fp is None else _ptr(fp), None if m is None else _ptr(m),
+                              None if rj is None else _ptr(rj), _ptr(pos), _ptr(ok))
+        assert rc == 0, rc
         return pos, ok.astype(bool)
 
     def canonical(self):

@@ -28,16 +28,55 @@ static uint32_t g_enc_plane_bytes = 0, g_enc_oob = 0;
 #include "mg_encode_core.h"
 
 namespace {
-struct Scratch {
-    std::vector<uint64_t> rec;
-    std::vector<uint32_t> head;
-    std::vector<uint8_t> act, fb, oflags, ord;
+// A workgroup's LDS on the host: exactly `bytes` bytes, 16-byte aligned, garbage before every batch, and a guard band
+// behind the last byte that nothing may touch.
+struct Lds {
+    static constexpr int kGuard = 64;
+    std::vector<uint8_t> mem;
+    uint8_t* base;
+    size_t bytes;
+    explicit Lds(size_t n) : mem(n + kGuard + 16), bytes(n) { base = mem.data() + ((16 - (reinterpret_cast<uintptr_t>(mem.data()) & 15)) & 15); }
+    void fill() { memset(base, 0xEE, bytes); memset(base + bytes, 0x5A, kGuard); }
+    bool intact() const {
+        for (int i = 0; i < kGuard; i++) if (base[bytes + i] != 0x5A) return false;
+        return true;
+    }
+};
+
+// [start, end) of every column of a carved StepScratch, in bytes from `base`; returns how many.  Lane per env: obj, rec,
+// head, act, fb, ord, oflags.  Fused (S = 8): rec, head, act, pflag, ordp, psc (`ord` IS ordp there, `rec_out` IS rec).
+int step_columns(const mg::StepScratch& sc, const uint8_t* base, int n, bool fused, int64_t* out) {
+    const int S = sc.S;
+    int c = 0;
+    auto col = [&](const void* p, size_t bytes) { out[2 * c] = (const uint8_t*)p - base; out[2 * c + 1] = out[2 * c] + (int64_t)bytes; c++; };
+    if (!fused) col(sc.obj, MG_MAX_OBJ * sizeof(MgObjDesc));
+    col(sc.rec, (size_t)n * S * 8);
+    col(sc.head, (size_t)MG_MT_HEAD * S * 4);
+    col(sc.act, (size_t)n * S);
+    if (fused) { col(sc.pflag, (size_t)n * S); col(sc.ordp, (size_t)n * S); col(sc.psc, (size_t)S * 4); }
+    else { col(sc.fb, (size_t)n * S); col(sc.ord, (size_t)n * S); col(sc.oflags, MG_MAX_OBJ); }
+    return c;
+}
+bool columns_ok(const mg::StepScratch& sc, const Lds& lds, int n, bool fused) {
+    int64_t e[16];
+    const int c = step_columns(sc, lds.base, n, fused, e);
+    for (int i = 0; i < c; i++) {
+        if (e[2 * i] < 0 || e[2 * i + 1] > (int64_t)lds.bytes) return false;
+        for (int j = 0; j < i; j++) if (e[2 * i] < e[2 * j + 1] && e[2 * j] < e[2 * i + 1]) return false;
+    }
+    return true;
+}
+
+// The LDS of a lane-per-env kernel (mg_step, mg_reset: lane_step_layout) for ONE env, S = 1
+struct LaneLds {
+    const MgConfig* cfg;
+    Lds lds;
     mg::StepScratch sc;
-    Scratch(const MgConfig* cfg) : rec(MG_MAX_AGENTS), head(MG_MT_HEAD), act(MG_MAX_AGENTS),
-                                   fb(MG_MAX_AGENTS), oflags(MG_MAX_OBJ, 0), ord(MG_MAX_AGENTS) {
-        for (int i = 1; i < cfg->n_obj; i++) oflags[i] = cfg->obj[i].flags;
-        sc.rec = rec.data(); sc.head = head.data(); sc.act = act.data(); sc.fb = fb.data(); sc.ord = ord.data();
-        sc.obj = cfg->obj; sc.oflags = oflags.data(); sc.S = 1; sc.col = 0;
+    explicit LaneLds(const MgConfig* c) : cfg(c), lds(mg::lane_step_bytes(c->n_agents, 1)), sc(mg::lane_step_scratch(lds.base, c->n_agents, 1, 0)) {}
+    bool ok() const { return columns_ok(sc, lds, cfg->n_agents, false); }
+    void begin() {          // a batch (of one env): garbage, then the shared tables as the kernels stage them
+        lds.fill();
+        mg::stage_obj_tables(*cfg, const_cast<MgObjDesc*>(sc.obj), const_cast<uint8_t*>(sc.oflags), 0, 1);
     }
 };
 }  // namespace
@@ -51,26 +90,39 @@ int emu_mt_seed(int B, const uint32_t* keys, const int32_t* key_len, uint32_t* m
     return 0;
 }
 
+// Return codes of the emulated launches: -100 bad arguments, -101 an unreported grid write, -102 / -103 the lanes of an
+// env disagree / a pending reset asks for the sequential loop, -104 a write behind the layout's last byte, -105 two
+// columns of the carving overlap or leave the byte count.
 int emu_reset(const MgConfig* cfg, const MgState* st, const MgGenProgram* prog, const uint8_t* mask) {
-    Scratch s(cfg);
+    LaneLds s(cfg);
+    if (!s.ok()) return -105;
     for (int b = 0; b < cfg->B; b++) {
         if (mask && !mask[b]) continue;
-        mg::reset_run(*cfg, *st, *prog, s.oflags.data(), b, mask != st->done, s.rec.data(), 1, 0);
+        s.begin();
+        mg::reset_run(*cfg, *st, *prog, s.sc.oflags, b, mask != st->done, s.sc.rec, 1, 0);
+        if (!s.lds.intact()) return -104;
     }
     return 0;
 }
 
+// ep: the mg_*_ep entry points' reset mode and episode outputs, or null (the plain step)
 int emu_step(const MgConfig* cfg, const MgState* st, const void* actions, int action_bytes, float* rewards,
-             const MgGenProgram* auto_reset) {
-    Scratch s(cfg);
+             const MgGenProgram* auto_reset, const MgEpisode* ep) {
+    if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return -100;
+    if (ep && ep->reset_mode == 1 && !auto_reset) return -100;
+    LaneLds s(cfg);
+    if (!s.ok()) return -105;
+    uint8_t* const fb = s.sc.fb;
+    s.sc.ep = ep;
+    s.sc.ep_rewards = ep ? rewards : nullptr;
     MgGenProgram none;
     memset(&none, 0, sizeof(none));
     const MgGenProgram& prog = auto_reset ? *auto_reset : none;
     for (int b = 0; b < cfg->B; b++) {
-        if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return -100;
+        s.begin();
         // odd envs without the pre-loaded front cells (StepScratch::fb == nullptr: the obs kernel's fused step reads its
         // staged grid directly), even envs with them (mg_step's kernel): the oracle comparison covers both
-        s.sc.fb = (b & 1) ? nullptr : s.fb.data();
+        s.sc.fb = (b & 1) ? nullptr : fb;
         const mg::StepEnv e = mg::step_load(*cfg, *st, actions, action_bytes, b, s.sc);
         // stepped on a staged copy of the grid slice, as the obs kernel does (mg_render.hip): the copy goes
         // back only when step_run reports it written — and must be unchanged when it does not
@@ -80,42 +132,45 @@ int emu_step(const MgConfig* cfg, const MgState* st, const void* actions, int ac
         s.sc.defer_writeback = (b % 3) == 2;
         const mg::StepOut out = mg::step_run(*cfg, *st, prog, auto_reset != nullptr, rewards, b, e, s.sc, staged.data());
         if (s.sc.defer_writeback) {
-            for (int k = 0; k < cfg->n_agents; k++) st->agents[(size_t)b * cfg->n_agents + k] = s.rec[k];
-            for (int j = 0; j < MG_MT_HEAD; j++) st->mt_head[(size_t)b * MG_MT_HEAD + j] = s.head[(j + out.head_k) & (MG_MT_HEAD - 1)];
+            for (int k = 0; k < cfg->n_agents; k++) st->agents[(size_t)b * cfg->n_agents + k] = s.sc.rec[k];
+            for (int j = 0; j < MG_MT_HEAD; j++) st->mt_head[(size_t)b * MG_MT_HEAD + j] = s.sc.head[(j + out.head_k) & (MG_MT_HEAD - 1)];
         }
-        const bool wrote = out.wrote;
-        if (wrote) memcpy(home, staged.data(), cfg->cells_stride);
+        if (out.wrote) memcpy(home, staged.data(), cfg->cells_stride);
         else if (memcmp(home, staged.data(), cfg->cells_stride) != 0) return -101;
+        if (!s.lds.intact()) return -104;
     }
     return 0;
 }
 
-// The obs kernel's fused step as a wave runs it (mg_render_kernel.h): batches of up to 8 staged envs in S = 8 columns,
-// step_begin on the env's lane, the agents resolved by one lane per (agent, env) — step_par_publish / _resolve / _commit,
-// here lane after lane with the phases in the kernel's order —, the sequential loop only for the envs that asked for it,
-// step_end.  *n_serial counts those envs.  More than 8 agents: the sequential step, as in the kernel.
+// The obs kernel's fused step as a wave runs it (mg_render_kernel.h): batches of up to 8 staged envs in S = 8 columns
+// (fused_step_layout), step_begin on the env's lane, the agents resolved by one lane per (agent, env) — step_par_publish /
+// _resolve / _commit, here lane after lane with the phases in the kernel's order —, the sequential loop only for the envs
+// that asked for it, step_end.  *n_serial counts those envs.  More than 8 agents: the sequential step, as in the kernel.
 int emu_step_par(const MgConfig* cfg, const MgState* st, const void* actions, int action_bytes, float* rewards,
-                 const MgGenProgram* auto_reset, int64_t* n_serial) {
-    if (cfg->n_agents > 8) return emu_step(cfg, st, actions, action_bytes, rewards, auto_reset);
+                 const MgGenProgram* auto_reset, const MgEpisode* ep, int64_t* n_serial) {
+    if (cfg->n_agents > 8) return emu_step(cfg, st, actions, action_bytes, rewards, auto_reset, ep);
     if (action_bytes != 1 && action_bytes != 4 && action_bytes != 8) return -100;
+    if (ep && ep->reset_mode == 1 && !auto_reset) return -100;
     const int n = cfg->n_agents, stride = cfg->cells_stride;
     MgGenProgram none;
     memset(&none, 0, sizeof(none));
     const MgGenProgram& prog = auto_reset ? *auto_reset : none;
-    std::vector<uint64_t> rec(n * 8), rec_out(n * 8);
-    std::vector<uint32_t> head(MG_MT_HEAD * 8);
-    std::vector<uint8_t> act(n * 8), pflag(n * 8), ordp(n * 8), oflags(MG_MAX_OBJ, 0), grids((size_t)8 * stride);
-    std::vector<int32_t> psc(8);
-    for (int i = 1; i < cfg->n_obj; i++) oflags[i] = cfg->obj[i].flags;
+    Lds lds(mg::fused_step_bytes(n));
+    // (the tables are the workgroup's own; on the GPU rec_out IS rec — the lanes run in lockstep —, here, lane after
+    // lane, the settled records wait beside the layout)
+    std::vector<uint8_t> oflags(MG_MAX_OBJ), grids((size_t)8 * stride);
+    std::vector<uint64_t> rec_out(n * 8);
+    mg::stage_obj_tables(*cfg, nullptr, oflags.data(), 0, 1);
+    mg::StepScratch sc = mg::fused_step_scratch(lds.base, n, 0, cfg->obj, oflags.data());
+    if (!columns_ok(sc, lds, n, true)) return -105;
+    sc.rec_out = rec_out.data();
+    sc.defer_writeback = true;
+    sc.ep = ep;
+    sc.ep_rewards = ep ? rewards : nullptr;
+    uint64_t* const rec = sc.rec;
     for (int b0 = 0; b0 < cfg->B; b0 += 8) {
         const int kb = cfg->B - b0 < 8 ? cfg->B - b0 : 8;
-        mg::StepScratch sc;
-        sc.rec = rec.data(); sc.head = head.data(); sc.act = act.data(); sc.fb = nullptr;
-        sc.obj = cfg->obj; sc.oflags = oflags.data(); sc.S = 8; sc.col = 0;
-        sc.pflag = pflag.data(); sc.ordp = ordp.data(); sc.psc = psc.data(); sc.rec_out = rec_out.data();
-        sc.defer_writeback = true;
-        memset(pflag.data(), 0xEE, pflag.size());
-        memset(ordp.data(), 0xEE, ordp.size());
+        lds.fill();
         mg::StepCtx ctx[8];
         for (int j = 0; j < kb; j++) {
             sc.col = j;
@@ -129,34 +184,61 @@ int emu_step_par(const MgConfig* cfg, const MgState* st, const void* actions, in
         for (int lane = 0; lane < 64; lane++) P[lane] = mg::step_par_resolve(*cfg, sc, grids.data(), kb, lane);
         for (int lane = 0; lane < 64; lane++) serial[lane] = mg::step_par_commit(*cfg, *st, rewards, b0, sc, P[lane], lane);
         for (int lane = 0; lane < 64; lane++)
-            if (P[lane].live && !serial[lane]) rec[lane] = rec_out[lane];        // (on the GPU rec_out IS rec: the lanes run in lockstep)
+            if (P[lane].live && !serial[lane]) rec[lane] = rec_out[lane];
         for (int j = 0; j < kb; j++) {
             const int b = b0 + j;
             sc.col = j;
             uint8_t* g = grids.data() + (size_t)j * stride;
             for (int k = 1; k < n; k++)
                 if (serial[k * 8 + j] != serial[j]) return -102;                      // every lane of an env gives the same answer
+            if (ctx[j].pending && serial[j]) return -103;                             // a reset call asks for nothing
             if (serial[j]) { mg::step_agents(*cfg, *st, rewards, b, sc, g, ctx[j]); if (n_serial) (*n_serial)++; }
             const mg::StepOut out = mg::step_end(*cfg, *st, prog, auto_reset != nullptr, b, sc, g, ctx[j]);
             for (int k = 0; k < n; k++) st->agents[(size_t)b * n + k] = rec[k * 8 + j];
-            for (int i = 0; i < MG_MT_HEAD; i++) st->mt_head[(size_t)b * MG_MT_HEAD + i] = head[((i + out.head_k) & (MG_MT_HEAD - 1)) * 8 + j];
+            for (int i = 0; i < MG_MT_HEAD; i++) st->mt_head[(size_t)b * MG_MT_HEAD + i] = sc.head[((i + out.head_k) & (MG_MT_HEAD - 1)) * 8 + j];
             uint8_t* home = st->grid + (size_t)b * stride;
             if (out.wrote) memcpy(home, g, stride);
             else if (memcmp(home, g, stride) != 0) return -101;
         }
+        if (!lds.intact()) return -104;
     }
     return 0;
 }
 
 int emu_place(const MgConfig* cfg, const MgState* st, int what, int x0, int y0, int x1, int y1, int max_tries,
               const int32_t* fixed_pos, const uint8_t* mask, const uint8_t* reject, int32_t* out_pos, uint8_t* out_ok) {
-    Scratch s(cfg);
+    LaneLds s(cfg);
+    if (!s.ok()) return -105;
     for (int b = 0; b < cfg->B; b++) {
         if (mask && !mask[b]) continue;
-        mg::place_run(*cfg, *st, s.oflags.data(), b, what, x0, y0, x1, y1, max_tries, fixed_pos, reject, out_pos, out_ok,
-                      s.rec.data(), 1, 0);
+        s.begin();
+        mg::place_run(*cfg, *st, s.sc.oflags, b, what, x0, y0, x1, y1, max_tries, fixed_pos, reject, out_pos, out_ok,
+                      s.sc.rec, 1, 0);
+        if (!s.lds.intact()) return -104;
     }
     return 0;
+}
+
+// The layouts and the view map themselves, for tests/test_step_scratch_host.py.  emu_step_columns: the columns' [start,
+// end) as the carve functions place them (fused: S is 8), `*total` the byte count; returns how many columns.
+int emu_step_columns(int fused, int n, int S, int64_t* out, int64_t* total) {
+    uint8_t* const base = reinterpret_cast<uint8_t*>(uintptr_t(1) << 20);      // (never dereferenced)
+    *total = fused ? (int64_t)mg::fused_step_bytes(n) : (int64_t)mg::lane_step_bytes(n, S);
+    return step_columns(fused ? mg::fused_step_scratch(base, n, 0, nullptr, nullptr) : mg::lane_step_scratch(base, n, S, 0), base, n,
+                        fused != 0, out);
+}
+int emu_step_lanes(int n_agents, int B) { return mg::step_lanes(n_agents, B); }
+int64_t emu_reset_scratch_bytes(int n, int S) { return (int64_t)mg::reset_scratch_bytes(n, S); }
+uint32_t emu_view_map(int x, int y, int dir, int vs, int off) { return mg::view_map(x, y, dir, vs, off); }
+// every cell of a view at once: out int32 [vs][vs][2], index [va][vb]
+void emu_view_world(uint32_t word0, int vs, int32_t* out) {
+    for (int va = 0; va < vs; va++)
+        for (int vb = 0; vb < vs; vb++) {
+            int wx, wy;
+            mg::view_world(word0, va, vb, &wx, &wy);
+            out[(va * vs + vb) * 2] = wx;
+            out[(va * vs + vb) * 2 + 1] = wy;
+        }
 }
 
 }  // extern "C"
@@ -290,6 +372,7 @@ int emu_encode_batch(const MgConfig* cfg, const MgState* st, uint8_t* out, int p
     return (int)g_enc_oob;
 }
 
+int emu_ep_sizeof(void) { return (int)sizeof(MgEpisode); }
 int emu_sizeof(int which) {
     switch (which) {
     case 0: return (int)sizeof(MgConfig);

@@ -1,5 +1,5 @@
 """Episode boundaries under auto-reset, on the host: the step bodies of marlgrid_amd/csrc/mg_core.h driven with an
-MgEpisode (tests/native/mg_hostemu_episode.cpp) — next-step reset (the terminal state is returned, the env's next call is
+MgEpisode (tests/native/mg_hostemu.cpp) — next-step reset (the terminal state is returned, the env's next call is
 its reset), same-step reset with the episode outputs, termination / truncation flags, episode length and return —
 against the oracle's independent envs sequenced the same way (tests/episode_ref.py).  Sequentially (`step_run`) and as the
 obs kernel's fused step runs (`step_begin` / `step_par_*` / `step_end` over batches of 8).

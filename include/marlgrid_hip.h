@@ -268,6 +268,24 @@ int32_t mg_step_render_encode(const MgConfig* cfg, const MgState* st, const void
                               float* rewards, const MgGenProgram* auto_reset, uint8_t* obs, uint8_t* encode_out,
                               void* stream);
 
+/* mg_step_render into a buffer that still holds what an earlier call of this function wrote there: the bands — one tile row of
+ * one agent's image, tile_size pixel rows — whose tiles are the ones that buffer was drawn from are not stored again.
+ * signature: device memory the caller keeps WITH `obs`, one per observation buffer, 16-byte aligned,
+ * B * MG_DELTA_SIG_BYTES(n_agents, view_size) bytes; per env the tile (orientation and overlay included) of every view cell of
+ * what `obs` holds: read, compared exactly — no hashes —, and rewritten by the call.  Its contents mean nothing to the caller.
+ * flags: MG_DELTA_FORCE — every band counts as changed and the signature is only recorded: the first call for a pair
+ * (obs, signature), and every call after anything else wrote into `obs` (mg_render_obs, the caller itself) or the atlas or the
+ * object table behind cfg changed — or, in stream order and therefore also for launches replayed from a captured graph, a
+ * signature filled with 0xFF bytes (the entry 0xFFFF is no tile: every band compares unequal).  The bytes in `obs` after the
+ * call are mg_step_render's.
+ * MG_E_UNSUPPORTED — nothing launched, call mg_step_render — unless: view 7 with 8-pixel tiles, at most 3 agents, no 'prestige'
+ * agent, grid and atlas in LDS. */
+#define MG_DELTA_FORCE 1u
+#define MG_DELTA_SIG_BYTES(n_agents, view_size) ((((n_agents) * (view_size) * (view_size) * 2) + 15) / 16 * 16)
+int32_t mg_step_render_delta(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes,
+                             float* rewards, const MgGenProgram* auto_reset, uint8_t* obs, uint16_t* signature,
+                             uint32_t flags, void* stream);
+
 /* obs: device uint8 [B][n][P][P][3].  Optional debug outputs (NULL to skip):
  * view_cells uint8 [B][n][vs][vs] (object id of the rotated sub-grid, index [i][j]),
  * view_agent uint8 [B][n][vs][vs] (shown agent index or 0xFF), vis_mask uint8 [B][n][vs][vs]. */

@@ -100,6 +100,14 @@ class PlaceStats(C.Structure):
                 ("all_ms", C.c_float * PLACE_ALL)]
 
 
+DELTA_FORCE = 1            # MG_DELTA_FORCE (mg_step_render_delta)
+
+
+def delta_sig_bytes(n_agents, view_size):
+    """MG_DELTA_SIG_BYTES: bytes per env of an observation buffer's signature"""
+    return (n_agents * view_size * view_size * 2 + 15) // 16 * 16
+
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libmarlgrid_hip.so")
 
 # every symbol include/marlgrid_hip.h declares
@@ -107,7 +115,8 @@ SYMBOLS = ["mg_abi_version", "mg_struct_sizes", "mg_host_flag_alloc", "mg_host_f
            "mg_render_obs",
            "mg_encode", "mg_put_obj", "mg_place", "mg_render_frame", "mg_time_render_obs",
            "mg_render_obs_lds_bytes", "mg_render_kernel_name", "mg_step_encode_views", "mg_encode_views",
-           "mg_episode_struct_size", "mg_step_ep", "mg_step_render_ep", "mg_step_encode_views_ep"]
+           "mg_episode_struct_size", "mg_step_ep", "mg_step_render_ep", "mg_step_encode_views_ep",
+           "mg_step_render_delta"]
 
 _lib = None
 _path = LIB_PATH
@@ -176,6 +185,8 @@ def lib():
     L.mg_step.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp]
     L.mg_step_render.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp]
     L.mg_step_render_encode.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp, vp]
+    # (cfg, st, actions, action_bytes, rewards, auto_reset, obs, signature, flags, stream)
+    L.mg_step_render_delta.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp, C.c_uint32, vp]
     L.mg_step_encode_views.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp]
     L.mg_encode_views.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp]
     L.mg_episode_struct_size.argtypes = []

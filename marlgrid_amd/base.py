@@ -417,7 +417,7 @@ class MultiGridEnv(object):
                  reward_decay=True, seed=1337, respawn=False, ghost_mode=True, agent_spawn_kwargs={},
                  batch_size=1, device=None, seeds=None, auto_reset=False, strict=True, obs_buffers=2,
                  fused_step=True, place_obs=True, encode_in_step=False, obs_format="image", episode_info=False,
-                 _dry=False):
+                 obs_delta="auto", _dry=False):
         if grid_size is not None:
             assert width is None and height is None
             width, height = grid_size, grid_size
@@ -473,6 +473,18 @@ class MultiGridEnv(object):
         self._encoded = obs_format == "encoded"
         self._enc_fused = True                 # until the library says MG_E_UNSUPPORTED for this configuration
         self._ep_fused = True                  # the same for mg_step_render_ep
+        # obs_delta: step() writes into a buffer set of the ring that still holds the observation of `obs_buffers` steps ago;
+        # with it the step's launch (mg_step_render_delta) compares, band by band — a tile row of an agent's image —, the tiles
+        # it is about to draw with the ones that buffer was drawn from (a signature tensor kept per buffer set) and does not
+        # store the bands that are the same: an agent that is blocked, done, or toggles / picks up / drops changes nothing.
+        # The returned tensors are VIEWS of buffers the env owns: a caller that writes into them calls invalidate_obs() (or
+        # constructs with obs_delta=False).  "auto": where the step is the one fused image launch without episode outputs or
+        # encode_in_step and the library has an instantiation for the shape (view 7, 8-pixel tiles, <= 3 agents, none
+        # 'prestige'); True: the same, but a configuration that cannot is an error; False: every step stores every byte.
+        if obs_delta not in ("auto", True, False):
+            raise ValueError("obs_delta must be 'auto', True or False (got %r)" % (obs_delta,))
+        self.obs_delta = obs_delta
+        self._delta_ok = obs_delta is not False     # until the library says MG_E_UNSUPPORTED for this configuration
         # where the observation buffers live: "search" (= True) picks the fastest of a bounded set of candidate
         # allocations by timing the raster itself into each (_place_obs_buffers -> mg_obs_place: <= 2 s, candidates <=
         # min(a quarter of the free memory, 32 GiB)); "thorough": the long search (a second pass, larger candidates, one
@@ -678,9 +690,18 @@ class MultiGridEnv(object):
                 g.obs = g.ring[0]
             self._ring = [dict(obs=self._groups[0].ring[i],
                                rewards=torch.zeros((B, n), dtype=torch.float32, device=dev),
-                               done=torch.zeros((B,), dtype=torch.uint8, device=dev))
+                               done=torch.zeros((B,), dtype=torch.uint8, device=dev),
+                               sig=None)       # (obs_delta: the signature of what `obs` holds, below)
                           for i in range(self.obs_buffers)]
             self._ring_i = 0
+            # obs_delta: per buffer set the tile map its observation was drawn from (MG_DELTA_SIG_BYTES per env), in DEVICE memory
+            # and invalidated there — filled with 0xFF: the entry 0xFFFF is no tile, every band compares unequal and is stored —,
+            # so that a captured step (torch.cuda.graph) sees an invalidation as an eager one does.  Made with the ring: step()
+            # allocates nothing.
+            self._delta_launches = 0
+            if self._delta_wanted():
+                for r in self._ring:
+                    r["sig"] = torch.full((B * N.delta_sig_bytes(n, self.view_size),), 0xFF, dtype=torch.uint8, device=dev)
             self.obs, self.rewards, self.done_t = (self._ring[0][k] for k in ("obs", "rewards", "done"))
             self.done_b = self.done_t.view(torch.bool)      # the same bytes, as the bool tensor step() returns
             # episode boundaries (mg_*_ep): the persistent return accumulator; per buffer set the step's outputs and, made
@@ -810,6 +831,7 @@ class MultiGridEnv(object):
         for i, r in enumerate(self._ring):
             r["obs"] = self._groups[0].ring[i]
         self.obs = self._ring[self._ring_i]["obs"]
+        self.invalidate_obs()               # (new buffers: no signature describes them)
         # (the torch-allocated ring tensors that were replaced are unreferenced now; their blocks stay in torch's caching
         # allocator for the caller's next allocations — this package does not empty a cache it does not own)
         if any_replaced:
@@ -1182,6 +1204,7 @@ class MultiGridEnv(object):
                 self._settings_seen = key
             return
         import torch
+        self.invalidate_obs()               # (a tile index means other pixels once the atlas or the object table changes)
         for g in self._groups:
             cfg, raw, flat, atlas = self._host_tables(g)
             # the obs kernel keeps 4 waves of per-env scratch (and the atlas, when it fits) in one workgroup's
@@ -1389,7 +1412,9 @@ class MultiGridEnv(object):
                 rc = L.mg_step_render_encode(*head, self.obs.data_ptr(), self._encoding_buffer().data_ptr(), stream)
                 self._enc_fused = encoding_written = rc != N.E_UNSUPPORTED
             if not encoding_written:
-                rc = L.mg_step_render(*head, self.obs.data_ptr(), stream)
+                rc = self._launch_step_delta(head, stream)
+                if rc is None:
+                    rc = L.mg_step_render(*head, self.obs.data_ptr(), stream)
         if rc is not None:
             N.check(rc)
         else:
@@ -1400,10 +1425,46 @@ class MultiGridEnv(object):
         if self.encode_in_step and not encoding_written:
             self._encode_into(self._encoding_buffer())
 
+    def _delta_wanted(self):
+        """obs_delta: is this env's step the launch that has a delta twin (and has the library not said no yet)"""
+        return (self._delta_ok and not self._encoded and self.fused_step and not self._hetero and not self._use_ep
+                and not self.encode_in_step)
+
+    def _launch_step_delta(self, head, stream):
+        """mg_step_render_delta into the current buffer set.  Whether a band is stored is decided on the device alone, against
+        the set's signature (an invalidated one matches nothing): the call is the same whatever happened to the set, so a
+        captured step replays correctly after any invalidation.  None: not this configuration, nothing launched."""
+        r = self._ring[self._ring_i]
+        if not self._delta_wanted() or r["sig"] is None:
+            if self.obs_delta is True:
+                raise NotImplementedError("obs_delta=True needs the fused image step without episode outputs, encode_in_step or "
+                                          "view groups, and a shape the library has a delta instantiation for")
+            return None
+        rc = self._lib.mg_step_render_delta(*head, self.obs.data_ptr(), r["sig"].data_ptr(), 0, stream)
+        if rc == N.E_UNSUPPORTED:
+            self._delta_ok = False
+            for q in self._ring:
+                q["sig"] = None
+            return self._launch_step_delta(head, stream)
+        self._delta_launches += 1
+        return rc
+
+    def invalidate_obs(self, buffer_set=None):
+        """The observation tensors reset() / step() return are views of buffers the env owns and writes again `obs_buffers`
+        steps later — with obs_delta only where the observation changed.  Call this after writing into one of them: the next
+        step into every buffer set (or into `buffer_set`, an index of the ring) stores every byte.  One small fill per set on
+        the current stream: ordered like a launch, and capturable."""
+        ring = getattr(self, "_ring", ())
+        for r in (ring if buffer_set is None else [ring[buffer_set]]):
+            if r.get("sig") is not None:
+                r["sig"].fill_(0xFF)
+
     def _launch_views(self, pixels=False):
         """one launch per view group (one group unless the agents' views differ) of the current state into the groups'
         observation buffers — encoded views: mg_encode_views —, or, `pixels`, the raster into their pixel buffers"""
         st, stream = C.byref(self._state), self._stream()
+        if not (self._encoded and pixels):
+            self.invalidate_obs(self._ring_i)       # (mg_render_obs writes the CURRENT set behind its signature's back)
         for g in self._groups:
             if self._encoded and not pixels:
                 N.check(self._lib.mg_encode_views(C.byref(g.cfg), st, g.obs.data_ptr(), stream))
@@ -1414,6 +1475,7 @@ class MultiGridEnv(object):
         import torch
         self._sync_tables()
         if debug:
+            self.invalidate_obs(self._ring_i)
             g = self._groups[0] if group is None else group
             B, nv, vs = self.batch_size, len(g.members), g.view_size
             cells = torch.zeros((B, nv, vs, vs), dtype=torch.uint8, device=self.device)
@@ -1678,6 +1740,7 @@ class MultiGridEnv(object):
                                                                                     tuple(getattr(self, k).shape)))
         for k in want - {"version"}:
             getattr(self, k).copy_(sd[k])
+        self.invalidate_obs()
         if bool((self.error_t != 0).any()):
             self._flag._host[0] = 1          # the restored batch carries recorded errors (whatever `strict` is:
                                              # check_errors() looks at the flag first)

@@ -167,12 +167,13 @@ int32_t mg_render_obs(const MgConfig* cfg, const MgState* st, uint8_t* obs, uint
 
 static int32_t step_render(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
                            const MgGenProgram* auto_reset, uint8_t* obs, uint8_t* encode_out, void* stream,
-                           const MgEpisode* ep = nullptr) {
+                           const MgEpisode* ep = nullptr, uint16_t* sig = nullptr, uint32_t sig_flags = 0) {
     const int e = check_step_args(cfg, st, actions, action_bytes, rewards, auto_reset, ep, true);
     if (e) return e;
     if (!obs) return MG_E_ARG;      // (every check between the state's and this one answers MG_E_ARG too)
     mg::RenderPick pick;
     if ((encode_out || ep) && !mg::render_pick(*cfg, ep ? mg::kEpisode : mg::kEncode, &pick)) return MG_E_UNSUPPORTED;
+    if (sig && !mg::render_pick(*cfg, mg::kDelta, &pick)) return MG_E_UNSUPPORTED;
     mg::FusedStep fs{};
     fs.actions = actions;
     fs.rewards = rewards;
@@ -186,6 +187,8 @@ static int32_t step_render(const MgConfig* cfg, const MgState* st, const void* a
     fs.enc_m_n = (uint32_t)((0x100000000ull + n - 1) / n);
     fs.has_ep = ep ? 1 : 0;
     if (ep) fs.ep = *ep;
+    fs.sig = sig;
+    fs.sig_force = (sig_flags & MG_DELTA_FORCE) ? 1 : 0;
     return rc(mg::launch_render(*cfg, *st, obs, nullptr, nullptr, nullptr, (hipStream_t)stream, &fs));
 }
 
@@ -203,6 +206,12 @@ int32_t mg_step_render_encode(const MgConfig* cfg, const MgState* st, const void
                               const MgGenProgram* auto_reset, uint8_t* obs, uint8_t* encode_out, void* stream) {
     if (!encode_out) return MG_E_ARG;
     return step_render(cfg, st, actions, action_bytes, rewards, auto_reset, obs, encode_out, stream);
+}
+
+int32_t mg_step_render_delta(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
+                             const MgGenProgram* auto_reset, uint8_t* obs, uint16_t* signature, uint32_t flags, void* stream) {
+    if (!signature || (flags & ~(uint32_t)MG_DELTA_FORCE) || (reinterpret_cast<uintptr_t>(signature) & 15)) return MG_E_ARG;
+    return step_render(cfg, st, actions, action_bytes, rewards, auto_reset, obs, nullptr, stream, nullptr, signature, flags);
 }
 
 int32_t mg_encode(const MgConfig* cfg, const MgState* st, const uint8_t* vis_mask, uint8_t* out, void* stream) {

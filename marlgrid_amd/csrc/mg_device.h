@@ -64,6 +64,8 @@ struct FusedStep {
                               //     4 k + dir —, (n_obj + 4 n) rounded up to 16 (mg_render_pick.h: render_enc_entries; 0: none)
     int32_t has_ep;           // mg_step_render_ep: `ep` is set — the launcher then takes an instantiation with the episode code
     MgEpisode ep;             //     compiled in (V + 32); the plain ones never look at either
+    uint16_t* sig;            // mg_step_render_delta (V + 64): per env the tmap — RenderScratch::tmap_stride bytes — of what `obs` holds
+    int32_t sig_force;        //     for it (null: not asked for); sig_force: every band counts as changed, the signature is only recorded
 };
 
 // x / d for small operands (x * d < 2^32) by multiply-high with ceil(2^32 / d): item index -> (slot, rest)

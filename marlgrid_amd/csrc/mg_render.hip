@@ -12,6 +12,7 @@ extern "C" int mg_ab_stamps(unsigned long long* p) { g_ab_stamps = p; return 0; 
 
 #if !defined(MG_DEV_ONLY)
 MG_RENDER_ALL(MG_RENDER_EXTERN)
+MG_RENDER_DELTA(MG_RENDER_EXTERN)
 #endif
 
 using RenderLauncher = hipError_t (*)(const MgConfig&, const MgState&, uint8_t*, uint8_t*, uint8_t*, uint8_t*, hipStream_t,
@@ -20,9 +21,16 @@ static RenderLauncher render_launcher(const RenderPick& p) {
 #define MG_RENDER_MATCH(VS, TS, WPB, V, RM) \
     if (p.vs == VS && p.ts == TS && p.wpb == WPB && p.v == V && p.rm == RM) return &launch_render_t<VS, TS, WPB, V, RM>;
     MG_RENDER_ALL(MG_RENDER_MATCH)
-#undef MG_RENDER_MATCH
     return nullptr;
 }
+// ... and a kDelta pick in its own list (mg_step_render_delta)
+static RenderLauncher render_delta_launcher(const RenderPick& p) {
+#if !defined(MG_DEV_ONLY)
+    MG_RENDER_DELTA(MG_RENDER_MATCH)
+#endif
+    return nullptr;
+}
+#undef MG_RENDER_MATCH
 
 #if defined(MG_AB_VARIANTS) || defined(MG_EXP) || defined(MG_DEV_ONLY)
 // Measurement and development builds only (libmarlgrid_hip_ab.so, `make exp`, -DMG_DEV_ONLY): another instantiation than the
@@ -67,8 +75,8 @@ hipError_t launch_render(const MgConfig& cfg, const MgState& st, uint8_t* obs, u
     FusedStep fs{};                 // no step: the raster alone
     fs.action_bytes = 8;
     if (fused_step) fs = *fused_step;
-    const RenderWant want = fs.has_ep ? kEpisode : fs.encode_out ? kEncode : kPlain;
-    if (fs.has_ep && fs.encode_out) return hipErrorInvalidValue;
+    const RenderWant want = fs.has_ep ? kEpisode : fs.encode_out ? kEncode : fs.sig ? kDelta : kPlain;
+    if ((fs.has_ep && fs.encode_out) || (fs.sig && want != kDelta)) return hipErrorInvalidValue;
     if ((view_cells || view_agent || vis_mask) && (want != kPlain || !(view_cells && view_agent && vis_mask))) return hipErrorInvalidValue;
     RenderPick p;
     if (!render_pick(cfg, want, &p)) return want == kPlain ? hipErrorInvalidValue : hipErrorNotSupported;
@@ -77,7 +85,8 @@ hipError_t launch_render(const MgConfig& cfg, const MgState& st, uint8_t* obs, u
     render_override(cfg, p);
     if (p.lds > (int)kRenderLdsMax) return hipErrorInvalidValue;
 #endif
-    const RenderLauncher launch = render_launcher(p);
+    RenderLauncher launch = render_launcher(p);
+    if (!launch && want == kDelta) launch = render_delta_launcher(p);
     if (!launch) return hipErrorInvalidValue;
     return launch(cfg, st, obs, view_cells, view_agent, vis_mask, s, fs, (size_t)p.lds);
 }

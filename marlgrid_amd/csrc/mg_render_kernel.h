@@ -250,6 +250,14 @@ extern unsigned long long* g_ab_stamps;       // set through mg_ab_stamps (mg_re
 //     off the fast path — `profiles/r06/ab_fused_encode_in_launch_as_a_flag_v23.txt`).
 // VX_ = V_ + 32: mg_step_render_ep's instantiations — the fused step takes its reset mode from an MgEpisode and writes the
 //     episode outputs (compiled in for the same reason; profiles/episodes/README.md: the plain ones keep their resources).
+// VX_ = V_ + 64: mg_step_render_delta's instantiations (MG_RENDER_DELTA, mg_render_pick.h) — the output buffer still holds what an
+//     earlier launch wrote into it, and `fs.sig` holds, per env, the tmap that launch drew it from.  A band (one tile row of one
+//     agent's image) whose VS tmap entries equal the recorded ones would be stored with the bytes that are already there: its
+//     stores are skipped.  The old signatures of a staged batch are requested with the staging loads (a load in the middle of
+//     the run drains the wave's store queue) into the envs' own tmap slots; the tmaps of the view group being derived and the
+//     group's band-mask words take the fused step's columns, which are free once the batch is stepped (the step's LDS-DMA landing
+//     zone moves from the tmap area to the view scratch): no LDS beyond the plain launch's.  Phase 5, a lane per band, compares
+//     and ORs the band's bit into the env's mask; the new signatures go back with stores nobody waits for.
 template <int VS_, int TS_, int WPB, int VX_ = 0, int RM_ = 0>
 __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState st, uint8_t* __restrict__ obs,
                                                         uint8_t* __restrict__ dbg_cells,
@@ -258,6 +266,7 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
     constexpr int V_ = VX_ & 15;                // the variant proper
     constexpr bool kEnc = (VX_ & 16) != 0;      // + 16: mg_step_render_encode
     constexpr bool kEp = (VX_ & 32) != 0;       // + 32: mg_step_render_ep — reset mode and episode outputs (MgEpisode) in the fused step
+    constexpr bool kDelta = (VX_ & 64) != 0;    // + 64: mg_step_render_delta — bands whose tiles equal the recorded signature are not stored
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     // the wave index is uniform: told to the compiler, everything derived from it (the wave's scratch
     // pointers, its run of envs, loop bounds) lives in SGPRs instead of one VGPR each
@@ -315,6 +324,7 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
     uint32_t* s_enc = reinterpret_cast<uint32_t*>(s_shared + lc.sh.total + (size_t)WPB * lc.L.total);
     constexpr bool kChunkRaster = TS_ > 0 && (TS_ % 8) == 0 && RM_ == 0;
     constexpr bool kStreamRaster = !kChunkRaster && !kGather;     // assemble-and-stream
+    static_assert(!kDelta || (kChunkRaster && VS_ == 7 && TS_ == 8 && V_ == 0 && !kEnc && !kEp), "mg_step_render_delta: the headline shape's fixed-lane raster");
     // the rasters bound by instruction issue run at a raised wave priority (phase 6); measured per instantiation: the gather
     // raster at 11-pixel tiles without 'prestige' agents is close enough to the HBM bound to lose 0.6 % by it
     constexpr bool kRasterPrio = (kGather && (TS_ <= 10 || V_ == 9)) || kStreamRaster;
@@ -379,6 +389,7 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
         depth = depth_mode > 0 ? depth_mode : kGather ? kGatherDepth : !kChunkRaster ? L.tmap_slots : kPrestige ? (1 << (wave & 3)) : (TS_ == 8 ? 2 : 1);
         if (depth > L.tmap_slots) depth = L.tmap_slots;
         if (depth > L.view_slots) depth = L.view_slots;   // (a group's views need a scratch slot per env)
+        if constexpr (kDelta) { if (depth > 2) depth = 2; }   // (the group's tmaps: two slots in the step's columns)
     }
     // item -> (slot, rest), view cell -> (viewer, row, column): 24-bit multiplies only (Div20; MG_REGION_LOCALS)
     constexpr bool kExactVV = VS_ > 0 && VS_ <= 9;     // 16 viewers * VS^2 cells: x * (m*d - 2^20) < 2^20 holds (checked below)
@@ -431,6 +442,23 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                 const int i = q * kWave + lanel;
                 v[q] = 4 * i < nd ? reinterpret_cast<const uint4*>(gsrc)[i] : make_uint4(0, 0, 0, 0);
             }
+            // (mg_step_render_delta) the batch's old signatures — one contiguous run —: requested here, before the batch's first store,
+            // and by LDS-DMA — lane l's 16 bytes to byte 16 l behind a wave-uniform address —: env j's signature lands in tmap slot j
+            // without passing through registers (three more uint4 per lane across this round trip were spilled)
+            constexpr int kSigQ = 3;                                        // render_delta_fits: a batch's signatures are <= 3 KiB
+            if constexpr (kDelta) {
+                const FusedStep& fsd = kernarg_again<FusedStep>(offsetof(RenderKernargs, fs));
+                const uint4* ssrc = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(fsd.sig) + (size_t)eb * L.tmap_stride);
+                const int ns = fsd.sig_force ? 0 : kb * (L.tmap_stride / 16);
+                typedef const __attribute__((address_space(1))) void* gptr;
+                typedef __attribute__((address_space(3))) void* lptr;
+#pragma unroll
+                for (int q = 0; q < kSigQ; q++) {
+                    const int i = q * kWave + lanel;
+                    if (i < ns) __builtin_amdgcn_global_load_lds((gptr)(ssrc + i), (lptr)(reinterpret_cast<uint8_t*>(w_tmap0) + q * kWave * 16), 16, 0, 0);
+                }
+            }
+            (void)kSigQ;
             const int r0i = lanel, r1i = lanel + kWave;                     // kb * n <= 8 * 16 = 2 * kWave records
             uint64_t rv0 = 0ull, rv1 = 0ull;
             double pv0 = 0., pv1 = 0.;
@@ -524,6 +552,7 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                 if (4 * i < nd) reinterpret_cast<uint4*>(w_stage_g)[i] = v[q];
             }
             for (int i = kSR * kWave + lanel; i < nd; i += kWave) reinterpret_cast<uint32_t*>(w_stage_g)[i] = gsrc[i];   // (grids beyond 2 KiB per batch: a second trip)
+            if constexpr (kDelta) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the old signatures are in their slots)
             if (!fs.enabled) {
                 if (r0i < nr) { const int j = (int)by_n.div((uint32_t)r0i); w_stage_r[j * rec_stride + (r0i - j * n)] = rv0; if constexpr (kPrestige) w_stage_p[j * rec_stride + (r0i - j * n)] = pv0; }
                 if (r1i < nr) { const int j = (int)by_n.div((uint32_t)r1i); w_stage_r[j * rec_stride + (r1i - j * n)] = rv1; if constexpr (kPrestige) w_stage_p[j * rec_stride + (r1i - j * n)] = pv1; }
@@ -639,6 +668,9 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                 sc.defer_writeback = true;      // records and RNG heads go back to HBM from the whole wave, below
                 // one-round-trip head refills through LDS-DMA (mt_generate16_dma): their landing zone, 9 rows of 128 bytes,
                 // is the tmap area — the views have not begun
+                // (mg_step_render_delta: the tmap slots hold the old signatures; the view scratch — vaff .. trow, in front of them — is as free)
+                if constexpr (kDelta) sc.dma = L.tmap - L.vaff >= kMtDmaBufDwords * 4 ? reinterpret_cast<uint32_t*>(ws + L.vaff) : nullptr;
+                else
                 sc.dma = (size_t)L.tmap_slots * L.tmap_stride >= kMtDmaBufDwords * 4 ? reinterpret_cast<uint32_t*>(w_tmap0) : nullptr;
                 // (mg_step_render_ep: a template value, not a branch — with it the plain instantiations stay at their register budget)
                 if constexpr (kEp) { sc.ep = &fs.ep; sc.ep_rewards = fs.rewards; }
@@ -700,9 +732,11 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                 {
                     uint64_t* rdst = st.agents + (size_t)eb * n;
                     uint32_t* hdst = st.mt_head + (size_t)eb * MG_MT_HEAD;
+                    int lane_w = lane;       // (mg_step_render_delta: opaque — what is derived from it below is not carried from the kernel's entry)
+                    if constexpr (kDelta) asm volatile("" : "+v"(lane_w));
 #pragma unroll
                     for (int q = 0; q < 2; q++) {
-                        const int i = lane + q * kWave;
+                        const int i = lane_w + q * kWave;
                         const int e = i >> 4, j = i & (MG_MT_HEAD - 1);             // head word j of env e
                         const int ke = __shfl(head_k, e & 7);
                         if (i < kb * MG_MT_HEAD) hdst[i] = sc.head[((j + ke) & (MG_MT_HEAD - 1)) * 8 + e];
@@ -763,7 +797,12 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
         if constexpr (kEnc) { if (enc_pending && ej0 > 0) encode_batch(true); }
         MG_REGION_LOCALS;
         const int e = eb + ej;
-        uint16_t* w_tmap = w_tmap0 + (size_t)(ej - ej0) * (L.tmap_stride / 2);
+        // (mg_step_render_delta: the group's tmaps in the step's columns — env ej's slot of w_tmap0 holds its old signature —, and
+        // behind the two of them the group's band masks, bit v * VS + view row: the band differs from what the buffer holds)
+        uint16_t* const w_tmap_g = kDelta ? reinterpret_cast<uint16_t*>(ws + L.step) : w_tmap0;
+        uint16_t* w_tmap = w_tmap_g + (size_t)(ej - ej0) * (L.tmap_stride / 2);
+        uint32_t* const w_chg = reinterpret_cast<uint32_t*>(ws + L.step + 2 * L.tmap_stride);
+        (void)w_chg;
         if (pass == 0) {
         // Views of the group's G envs at once (phases 1-5 -> one tmap slot each; G: where `depth` is chosen).  Phases 2
         // and 4 have one lane per AGENT / VIEWER — a lone env leaves 61 of 64 lanes idle — and 3 x 49 view cells fill
@@ -782,6 +821,7 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                 if (has_second) reinterpret_cast<uint32_t*>(w_second)[i] = 0xFFFFFFFFu;
             }
         for (int i = lane; i < G * L.trow_stride; i += kWave) w_trow[i] = 0;
+        if constexpr (kDelta) { if (lane < 2) w_chg[lane] = 0; }
         wave_lds_sync();
         if constexpr (V_ == 3 || V_ == 4) {
             for (int g = 0; g < G; g++)
@@ -988,6 +1028,21 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                 const uint32_t g = by_nvVS.div(it), r = it - __umul24(g, nvVS);          // r = viewer * VS + view row
                 const uint32_t mask = w_vis[__umul24(g, (uint32_t)L.trow_stride) + r];
                 uint16_t* row = w_tmap + __umul24(g, (uint32_t)(L.tmap_stride / 2)) + __umul24(r, (uint32_t)VS);
+                if constexpr (kDelta) {
+                    // the band's final tiles against the recorded ones (exact: the entry — tile, orientation, overlay — is the pixels)
+                    // (an entry is a multiple of the tile's dwords and below the atlas's size: 0xFFFF is none — a signature a host
+                    // has filled with 0xFF, in stream order, makes every band count as changed)
+                    const uint16_t* orow = w_tmap0 + __umul24((uint32_t)ej + g, (uint32_t)(L.tmap_stride / 2)) + __umul24(r, (uint32_t)VS);
+                    uint32_t diff = (uint32_t)kernarg_again<FusedStep>(offsetof(RenderKernargs, fs)).sig_force;
+#pragma unroll
+                    for (int va = 0; va < VS_; va++) {
+                        const bool vis = (mask >> va) & 1u;
+                        const uint32_t nw = vis ? (uint32_t)row[va] : 0u;
+                        diff |= nw ^ (uint32_t)orow[va];
+                        if (!vis) row[va] = 0;
+                    }
+                    if (diff) atomicOr(&w_chg[g], 1u << r);
+                } else
                 for (int va = 0; va < VS; va++)
                     if (!((mask >> va) & 1u)) row[va] = 0;
                 if (dbg_cells) {
@@ -1001,6 +1056,10 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
         }
         }
         wave_lds_sync();
+        if constexpr (kDelta) {        // the group's new signatures, as the run of 16-byte pieces they are (the padding of a slot: whatever is there)
+            uint4* sdst = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(kernarg_again<FusedStep>(offsetof(RenderKernargs, fs)).sig) + (size_t)e * L.tmap_stride);
+            for (int i = lane; i < G * (L.tmap_stride / 16); i += kWave) sdst[i] = reinterpret_cast<const uint4*>(w_tmap_g)[i];
+        }
         } else {
         if constexpr (kPrestige) {
             // 4b. tiles of active 'prestige' agents are recoloured per env (render_post) — and blended
@@ -1176,7 +1235,11 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
             constexpr bool kFixedLane = VS_ > 0 && LU >= 60 && V_ != 6;
             if constexpr (kFixedLane) {
                 constexpr uint32_t PRc = RBc / 8u;                                          // pairs per pixel row
-                const uint32_t q = (uint32_t)lane % PC, grp = (uint32_t)lane / PC;
+                // (mg_step_render_delta — one register over the plain kernel's budget —: the lane index opaque, so that the lane's
+                // constants below are worked out per env instead of being carried, spilled, across the whole env loop)
+                int lane_r = lane;
+                if constexpr (kDelta) asm volatile("" : "+v"(lane_r));
+                const uint32_t q = (uint32_t)lane_r % PC, grp = (uint32_t)lane_r / PC;
                 uint32_t rowpar[2], vaq[2], kp2[2];
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
@@ -1197,12 +1260,29 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                 };
                 constexpr int CSF = (int)LU;
                 int base = 0;                                                               // first chunk of the trip (uniform)
+                // mg_step_render_delta: a chunk lies in ONE band (a period is PRW rows, a band a whole number of periods), and a
+                // four-trip block is a whole number of bands (24 pixel rows = 3 at view 7): a block without a changed band is passed
+                // over on a wave-uniform test, one with all of them stores as the plain kernel does, and in between a lane stores
+                // the trips whose band changed
+                constexpr uint32_t kBlockRows = 4u * PRW * GPT, kBlockBands = kBlockRows / TS_, kBlockMask = (1u << kBlockBands) - 1u;
+                static_assert(!kDelta || (kBlockRows % TS_ == 0 && TS_ % PRW == 0), "whole bands per block, whole periods per band");
+                uint32_t chg = 0xFFFFFFFFu, bshift = 0;
+                if constexpr (kDelta) chg = (uint32_t)__builtin_amdgcn_readfirstlane((int)w_chg[ej - ej0]);
+                (void)chg; (void)bshift;
                 for (; base + 4 * CSF <= total; base += 4 * CSF) {                          // four WHOLE trips at a time
+                    uint32_t bm = kBlockMask;
+                    if constexpr (kDelta) {
+                        bm = (chg >> bshift) & kBlockMask;
+                        bshift += kBlockBands;
+                        if (bm == 0) { rcur += 4u * PRW * GPT; continue; }
+                    }
                     if (live) {                                                             // (one exec mask for all of it)
                         const int c = base + lane;
                         uint32_t ti[8], of[8];
+                        uint32_t keep = 0;
 #pragma unroll
                         for (int t = 0; t < 4; t++) {
+                            if constexpr (kDelta) keep |= ((chg >> ((rcur + rowpar[0]) / (uint32_t)TS_)) & 1u) << t;
                             coords(rcur + rowpar[0], 0, ti[2 * t], of[2 * t]);
                             coords(rcur + rowpar[1], 1, ti[2 * t + 1], of[2 * t + 1]);
                             rcur += PRW * GPT;
@@ -1221,6 +1301,11 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
 #pragma unroll
                             for (int i = 0; i < 8; i++) pp[i] = make_uint2(0x1e19231eu, 0x231e1923u);
                         }
+                        if (kDelta && bm != kBlockMask) {
+#pragma unroll
+                            for (int t = 0; t < 4; t++)
+                                if ((keep >> t) & 1u) put(c + t * CSF, make_uint4(pp[2 * t].x, pp[2 * t].y, pp[2 * t + 1].x, pp[2 * t + 1].y));
+                        } else
 #pragma unroll
                         for (int t = 0; t < 4; t++) put(c + t * CSF, make_uint4(pp[2 * t].x, pp[2 * t].y, pp[2 * t + 1].x, pp[2 * t + 1].y));
                     }
@@ -1230,8 +1315,9 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                     uint32_t ti0, of0, ti1, of1;
                     coords(rcur + rowpar[0], 0, ti0, of0);
                     coords(rcur + rowpar[1], 1, ti1, of1);
+                    const bool changed = !kDelta || ((chg >> ((rcur + rowpar[0]) / (uint32_t)TS_)) & 1u);
                     rcur += PRW * GPT;
-                    if (live && c < total) {
+                    if (live && c < total && changed) {
                         uint2 p0, p1;
                         if constexpr (V_ != 4) { p0 = ld_pair(tile_dword((uint32_t)w_tmap[ti0]) + of0); p1 = ld_pair(tile_dword((uint32_t)w_tmap[ti1]) + of1); }
                         else { p0 = make_uint2(0x1e19231eu, 0x231e1923u); p1 = p0; }

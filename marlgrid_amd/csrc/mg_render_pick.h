@@ -173,7 +173,9 @@ constexpr size_t kRenderLdsMax = 160 * 1024;
 struct RenderPick { int vs, ts, wpb, v, rm, lds; };
 // what the launch has to do besides the raster: nothing (mg_render_obs, mg_step_render), MultiGrid.encode of the stepped batch
 // (mg_step_render_encode: the instantiations V + 16, MG_RENDER_GROUP_N), the episode outputs (mg_step_render_ep: V + 32, group P)
-enum RenderWant { kPlain, kEncode, kEpisode };
+// ... or the band-wise comparison against the signature of what the output buffer already holds (mg_step_render_delta: V + 64,
+// MG_RENDER_DELTA — a list of its own, not part of MG_RENDER_ALL)
+enum RenderWant { kPlain, kEncode, kEpisode, kDelta };
 
 // dwords of the fused encode's LDS table — one per grid byte value, (n_obj + 4 n) rounded up to 16 —, 0: object ids and
 // agent marks do not share a byte, no fused encode
@@ -211,6 +213,17 @@ inline int render_min_lds_bytes(const MgConfig& cfg) {
 // over 4-wave workgroups at the bench batch.  Small batches keep 4-wave workgroups so that they
 // still spread over all CUs.
 inline int choose_wpb(const MgConfig& cfg, int mode) { return cfg.B >= 4096 && render_fits(cfg, 16, mode) ? 16 : 4; }
+
+// mg_step_render_delta (V + 64), what its instantiations take from a wave's scratch WITHOUT growing it: the old signatures of a
+// staged batch land in the envs' own tmap slots with the staging loads (three 16-byte requests per lane: 3 KiB at most); the tmaps
+// of the view group being derived — two envs at 8-pixel tiles — and the group's two band-mask words live in the fused step's
+// columns (free once the batch is stepped); a band mask is one word (nv * vs bands).  At most three agents — whatever the grid
+// leaves of the batch size — is what all of it holds for.
+MG_LAYOUT_FN bool render_delta_fits(const MgConfig& cfg, const RenderScratch& L) {
+    const int nv = cfg.n_view ? cfg.n_view : cfg.n_agents;
+    return cfg.n_view == 0 && cfg.n_agents <= 3 && nv * cfg.view_size <= 32 && L.stage_envs * L.tmap_stride <= 3 * 64 * 16 &&
+           2 * L.tmap_stride + 16 <= round_up((int)fused_step_bytes(cfg.n_agents), 16);
+}
 
 // The one rule set.  false: no instantiation for this `want` (the C ABI answers MG_E_UNSUPPORTED: hosts take the plain step
 // launch and mg_encode, or mg_step_ep and mg_render_obs) or the launch does not fit LDS (mg_render_obs_lds_bytes).  Every
@@ -275,8 +288,10 @@ inline bool render_pick(const MgConfig& cfg, RenderWant want, RenderPick* out) {
         // Not: a grid read in place, 'prestige' agents, an atlas in global memory (all V != 0).
         const bool shape = p.v == 0 && ((p.rm == 2 && p.vs == 7 && p.ts == 5) ||
                                         (p.rm == 0 && p.ts == 8 && (p.vs == 7 || p.vs == 9 || (p.vs == 0 && vs > 9))));
-        if (!shape) return false;
-        p.v |= want == kEncode ? 16 : 32;
+        // (mg_step_render_delta: the headline shape alone — view 7 at 8-pixel tiles, the fixed-lane chunk raster — with few enough
+        // agents for render_delta_fits)
+        if (want == kDelta ? !(shape && p.rm == 0 && p.vs == 7 && render_delta_fits(cfg, render_scratch_for(cfg, p.wpb, 0))) : !shape) return false;
+        p.v |= want == kEncode ? 16 : want == kEpisode ? 32 : 64;
         if (want == kEncode) {
             // the encode's table has to fit beside FOUR waves of scratch, whatever the batch: render_scratch_for fills LDS with staged
             // envs, so a larger workgroup's leaner layout may fit where this one does not — such a configuration has no fused encode
@@ -350,6 +365,9 @@ inline bool render_pick(const MgConfig& cfg, RenderWant want, RenderPick* out) {
 #define MG_RENDER_GROUP_P(X) /* mg_step_render_ep (V + 32): the shapes of group N */                                       \
     X(7, 8, 16, 32, 0) X(7, 8, 4, 32, 0) X(9, 8, 16, 32, 0) X(9, 8, 4, 32, 0) X(0, 8, 8, 32, 0) X(0, 8, 4, 32, 0)                       \
     X(7, 5, 16, 32, 2) X(7, 5, 4, 32, 2)
+// mg_step_render_delta (V + 64): NOT part of MG_RENDER_ALL — the launcher looks a kDelta pick up in this list (inst group Q)
+#define MG_RENDER_DELTA(X) X(7, 8, 16, 64, 0) X(7, 8, 4, 64, 0)
+#define MG_RENDER_GROUP_Q(X) MG_RENDER_DELTA(X)
 // every instantiation of this build (the headline shape's group first: the launcher's lookup walks the list in order)
 #if defined(MG_DEV_ONLY)      // development: compile ONE instantiation (register / ISA checks without the other hundred), e.g. -DMG_DEV_ONLY="7,5,16,0,0"
 #define MG_RENDER_ONE(X, ...) X(__VA_ARGS__)

@@ -30,6 +30,8 @@
  *   mg_render_frame MultiGridEnv.render's whole-grid image: MultiGrid.render(top_agent=None) +
  *                   visibility highlight         (base.py:714-759, 301-331)
  *   mg_render_kernel_name  (no reference counterpart: names the launch for profiles and warns of generic instantiations)
+ *   mg_render_specialize   (none either: compiles, at run time, the instantiation of the observation kernel a (view_size,
+ *                   tile_size) pair off the library's table would have; mg_step_render_spec / mg_render_obs_spec launch it)
  *   mg_obs_place    the observation arrays MultiGridEnv's constructor / gen_obs allocate (base.py:334-347, 453-474),
  *                   for a batch: where in HBM they lie (construction time; mg_obs_release, mg_obs_trim)
  *
@@ -58,7 +60,9 @@
 #ifndef MARLGRID_HIP_H
 #define MARLGRID_HIP_H
 
+#if !defined(__HIPCC_RTC__)   /* (hipRTC has no system headers: the source that includes this file supplies the types) */
 #include <stdint.h>
+#endif
 
 #ifdef __cplusplus
 extern "C" {
@@ -345,6 +349,58 @@ int32_t mg_step_render_ep(const MgConfig* cfg, const MgState* st, const void* ac
 int32_t mg_step_encode_views_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes,
                                 float* rewards, const MgGenProgram* auto_reset, uint8_t* views, const MgEpisode* ep,
                                 void* stream);
+
+/* ---- the observation kernel specialised on demand (mg_rtc.hip) -------------------------------------------------------
+ *
+ * The library ships ~100 instantiations of its observation kernel; a (view_size, tile_size) pair off that table runs the
+ * instantiation that reads both at run time (mg_render_kernel_name's bits), 2-2.4x slower.  mg_render_specialize compiles
+ * the instantiation the configuration would have if it were on the table — from the library's own headers, the files next
+ * to it (marlgrid_amd/csrc/ and include/ of the tree it was built in; refused when they are not the ones it was built from),
+ * with hipRTC (libhiprtc is loaded at the first call; the library loads without it) — and returns a
+ * handle that mg_step_render_spec / mg_render_obs_spec launch instead of the table's entry.  Same arguments, same bytes
+ * written as mg_step_render[_encode | _ep] / mg_render_obs.
+ *
+ * want: 0 the plain step / raster, 1 with the encode (mg_step_render_encode), 2 with the episode outputs (mg_step_render_ep).
+ * arch: "gfx950", or NULL: the current device's.  cache_dir: a directory for compiled code objects (created if missing;
+ * files are written under a temporary name and renamed, validated by length and checksum before they are loaded), or NULL.
+ * flags: MG_SPEC_COMPILE_ONLY — compile (or read the cache) and fill `info` without touching a device; needs `arch`;
+ * *handle stays NULL.  A handle belongs to the device that was current when it was made and to the shape (B's side of
+ * 4096, agents, grid, view, tiles, tables) of `cfg`: the launch calls answer MG_E_ARG for a config whose pick differs.
+ * Compiled code is kept per process: a second handle for the same instantiation and arch (another device, another env)
+ * loads it without compiling (info->cache_hit = 1: memory, 2: cache_dir).
+ *
+ * MG_E_UNSUPPORTED, with the reason in info->reason: the table's instantiation is already the specialised one, or the
+ * configuration is one that is not specialised ('prestige' agents, a grid or an atlas read in place, views under 3);
+ * libhiprtc or the headers are missing; the compile failed; the instantiation needs scratch memory (spilled registers) even with 4-wave
+ * workgroups — workgroups are stepped down 16 -> 8 -> 4 before that. */
+#define MG_SPEC_COMPILE_ONLY 1u
+typedef struct MgSpecInfo {
+    char kernel_name[96];   /* "mg::render_kernel<VS, TS, WPB, V, RM>", mg_render_kernel_name's format */
+    int32_t vs, ts, wpb, v, rm;
+    int32_t lds_bytes;      /* LDS of one workgroup */
+    int32_t lds_static;     /* 1: compiled in as a static array (workgroups over 64 KiB), 0: asked for at the launch */
+    int32_t scratch_bytes;  /* private segment per work-item: 0 for every instantiation that is accepted */
+    int32_t code_bytes;     /* the code object */
+    int32_t cache_hit;      /* 0 compiled now, 1 taken from this process's memory, 2 read from cache_dir */
+    int32_t table_is_ideal; /* MG_E_UNSUPPORTED because the table's instantiation is already the specialised one: nothing is missing */
+    int32_t reserved0;
+    double compile_seconds; /* 0 on a hit */
+    char reason[256];       /* MG_E_UNSUPPORTED: why */
+} MgSpecInfo;
+int32_t mg_spec_info_struct_size(void);   /* sizeof(MgSpecInfo) as this build sees it */
+int32_t mg_render_specialize(const MgConfig* cfg, int32_t want, uint32_t flags, const char* arch, const char* cache_dir,
+                             void** handle, MgSpecInfo* info);
+/* mg_step_render (encode_out == NULL, ep == NULL), mg_step_render_encode (encode_out) or mg_step_render_ep (ep) — the one
+ * the handle was made for (MG_E_ARG otherwise) — through the handle's instantiation. */
+int32_t mg_step_render_spec(void* handle, const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes,
+                            float* rewards, const MgGenProgram* auto_reset, uint8_t* obs, uint8_t* encode_out,
+                            const MgEpisode* ep, void* stream);
+/* mg_render_obs without the debug outputs (a handle made with want 0) */
+int32_t mg_render_obs_spec(void* handle, const MgConfig* cfg, const MgState* st, uint8_t* obs, void* stream);
+int32_t mg_render_spec_release(void* handle);   /* unloads the handle's module (on its device); NULL: nothing */
+/* the sources mg_render_specialize compiles from, as the library read and accepted them: the count (0: missing, or not the
+ * build's), and entry `i`'s name / text / length (tests: with the library's other sources they hash to mg_build_info's id) */
+int32_t mg_rtc_source(int32_t i, const char** name, const char** text, int32_t* length);
 
 /* The same views of the current state (after mg_reset / mg_step), for one view group's cfg: views [B][nv][vs][vs][3] with
  * nv = n_view, or n_agents when n_view == 0.  Tile size and atlas play no part. */

@@ -102,6 +102,22 @@ class PlaceStats(C.Structure):
 
 DELTA_FORCE = 1            # MG_DELTA_FORCE (mg_step_render_delta)
 
+SPEC_COMPILE_ONLY = 1      # MG_SPEC_COMPILE_ONLY (mg_render_specialize)
+WANT_PLAIN, WANT_ENCODE, WANT_EPISODE = 0, 1, 2
+
+
+class SpecInfo(C.Structure):
+    """MgSpecInfo: what mg_render_specialize says about the instantiation it compiled (or why it did not)"""
+    _fields_ = [("kernel_name", C.c_char * 96), ("vs", C.c_int32), ("ts", C.c_int32), ("wpb", C.c_int32), ("v", C.c_int32),
+                ("rm", C.c_int32), ("lds_bytes", C.c_int32), ("lds_static", C.c_int32), ("scratch_bytes", C.c_int32),
+                ("code_bytes", C.c_int32), ("cache_hit", C.c_int32), ("table_is_ideal", C.c_int32), ("reserved0", C.c_int32),
+                ("compile_seconds", C.c_double), ("reason", C.c_char * 256)]
+
+    def as_dict(self):
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f != "reserved0"}
+        d["kernel_name"], d["reason"] = self.kernel_name.decode(), self.reason.decode()
+        return d
+
 
 def delta_sig_bytes(n_agents, view_size):
     """MG_DELTA_SIG_BYTES: bytes per env of an observation buffer's signature"""
@@ -116,7 +132,9 @@ SYMBOLS = ["mg_abi_version", "mg_struct_sizes", "mg_host_flag_alloc", "mg_host_f
            "mg_encode", "mg_put_obj", "mg_place", "mg_render_frame", "mg_time_render_obs",
            "mg_render_obs_lds_bytes", "mg_render_kernel_name", "mg_step_encode_views", "mg_encode_views",
            "mg_episode_struct_size", "mg_step_ep", "mg_step_render_ep", "mg_step_encode_views_ep",
-           "mg_step_render_delta"]
+           "mg_step_render_delta",
+           "mg_spec_info_struct_size", "mg_render_specialize", "mg_step_render_spec", "mg_render_obs_spec",
+           "mg_render_spec_release", "mg_rtc_source"]
 
 _lib = None
 _path = LIB_PATH
@@ -200,6 +218,19 @@ def lib():
     L.mg_step_encode_views_ep.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp,
                                           C.POINTER(Episode), vp]
     L.mg_render_obs.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp, vp, vp, vp]
+    L.mg_spec_info_struct_size.argtypes = []
+    L.mg_spec_info_struct_size.restype = i32
+    if L.mg_spec_info_struct_size() != C.sizeof(SpecInfo):
+        raise ImportError("marlgrid_amd: MgSpecInfo is %d bytes in %s, %d in marlgrid_amd/_native.py"
+                          % (L.mg_spec_info_struct_size(), path, C.sizeof(SpecInfo)))
+    # (cfg, want, flags, arch, cache_dir, &handle, &info)
+    L.mg_render_specialize.argtypes = [C.POINTER(Config), i32, C.c_uint32, C.c_char_p, C.c_char_p, C.POINTER(vp), C.POINTER(SpecInfo)]
+    # (handle, cfg, st, actions, action_bytes, rewards, auto_reset, obs, encode_out, ep, stream)
+    L.mg_step_render_spec.argtypes = [vp, C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp,
+                                      C.POINTER(Episode), vp]
+    L.mg_render_obs_spec.argtypes = [vp, C.POINTER(Config), C.POINTER(State), vp, vp]
+    L.mg_render_spec_release.argtypes = [vp]
+    L.mg_rtc_source.argtypes = [i32, C.POINTER(C.c_char_p), C.POINTER(vp), C.POINTER(i32)]
     L.mg_encode.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp, vp]
     L.mg_put_obj.argtypes = [C.POINTER(Config), C.POINTER(State), i32, i32, i32, vp, vp]
     L.mg_place.argtypes = [C.POINTER(Config), C.POINTER(State), i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]

@@ -405,6 +405,8 @@ class _ViewGroup(object):
         self.cfg = self.atlas = self.atlas_dev = None
         self.ring = []                                   # obs tensors (B, n_g, P, P, 3), one per buffer set
         self.obs = None
+        self.spec = {}                                   # specialize: want (N.WANT_*) -> handle of mg_render_specialize, or None
+        self.spec_info = {}                              # ... and what the library said about it (MgSpecInfo as a dict)
 
 
 class MultiGridEnv(object):
@@ -417,7 +419,7 @@ class MultiGridEnv(object):
                  reward_decay=True, seed=1337, respawn=False, ghost_mode=True, agent_spawn_kwargs={},
                  batch_size=1, device=None, seeds=None, auto_reset=False, strict=True, obs_buffers=2,
                  fused_step=True, place_obs=True, encode_in_step=False, obs_format="image", episode_info=False,
-                 obs_delta="auto", _dry=False):
+                 obs_delta="auto", specialize=False, specialize_cache=None, _dry=False):
         if grid_size is not None:
             assert width is None and height is None
             width, height = grid_size, grid_size
@@ -485,6 +487,22 @@ class MultiGridEnv(object):
             raise ValueError("obs_delta must be 'auto', True or False (got %r)" % (obs_delta,))
         self.obs_delta = obs_delta
         self._delta_ok = obs_delta is not False     # until the library says MG_E_UNSUPPORTED for this configuration
+        # specialize: the library ships ~100 instantiations of the observation kernel; a (view_size, view_tile_size) pair off
+        # that table runs the fully run-time one (the RuntimeWarning of _warn_generic_kernel), 2-2.4x slower.  "auto" / True: the
+        # instantiation this configuration would have on the table is compiled when the env is built (mg_render_specialize: hipRTC,
+        # ~5 s per instantiation, once per process and — through `specialize_cache` — once per machine) and launched instead, per
+        # view group; the variants with encode_in_step and with episode outputs are compiled when a step first needs them.  The
+        # bytes written are the table kernel's.  Where the library has nothing to compile — 'prestige' agents, a grid or an atlas
+        # read in place, no libhiprtc —, "auto" keeps the table's kernel (and its warning), True raises NotImplementedError with
+        # the library's reason; a shape the table already has compiled in is no error.  False (the default): launches, kernel names
+        # and warnings are exactly the table's.  specialize_cache: a directory for compiled code objects; None: $MARLGRID_AMD_CACHE,
+        # else ~/.cache/marlgrid_amd; False: none.  Encoded views (obs_format="encoded") rasterise nothing: not specialised.
+        if specialize not in ("auto", True, False):
+            raise ValueError("specialize must be False, 'auto' or True (got %r)" % (specialize,))
+        self.specialize = specialize
+        if specialize_cache is None:
+            specialize_cache = os.environ.get("MARLGRID_AMD_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "marlgrid_amd")
+        self._spec_cache = os.fsencode(specialize_cache) if specialize and specialize_cache else None
         # where the observation buffers live: "search" (= True) picks the fastest of a bounded set of candidate
         # allocations by timing the raster itself into each (_place_obs_buffers -> mg_obs_place: <= 2 s, candidates <=
         # min(a quarter of the free memory, 32 GiB)); "thorough": the long search (a second pass, larger candidates, one
@@ -654,6 +672,55 @@ class MultiGridEnv(object):
         (mg_render_kernel_name) and as rocprofv3 prints it"""
         self._sync_tables()
         return self._groups[0].kernel_name
+
+    @property
+    def specialization(self):
+        """specialize: what mg_render_specialize made for this env so far — one MgSpecInfo dict (kernel_name, the five
+        parameters, lds_bytes, scratch_bytes, code_bytes, compile_seconds, cache_hit; request_seconds: the whole call, load
+        included) per handle, view group by view group, with `group` and `want` (0 plain, 1 with the encode, 2 with episode outputs)"""
+        self._sync_tables()
+        return [dict(g.spec_info[w], group=k, want=w) for k, g in enumerate(self._groups) for w in sorted(g.spec) if g.spec[w]]
+
+    def _spec(self, g, want):
+        """the group's handle for `want` (N.WANT_PLAIN / _ENCODE / _EPISODE), asked for on first use; None: the table's launch"""
+        if not self.specialize or self._encoded:
+            return None
+        if want not in g.spec:
+            import torch
+            info, h = N.SpecInfo(), C.c_void_p()
+            if self._spec_cache:
+                try:
+                    os.makedirs(self._spec_cache, exist_ok=True)
+                except OSError:                  # (a home that cannot be written: compile without a cache)
+                    self._spec_cache = None
+            import time
+            t0 = time.perf_counter()
+            with torch.cuda.device(self.device):      # (a handle belongs to the device it is loaded on)
+                rc = self._lib.mg_render_specialize(C.byref(g.cfg), want, 0, None, self._spec_cache, C.byref(h), C.byref(info))
+            g.spec_info[want] = dict(info.as_dict(), request_seconds=time.perf_counter() - t0)      # (compile or cache read, and the load)
+            if rc == N.E_UNSUPPORTED:
+                g.spec[want] = None
+                if self.specialize is True and not info.table_is_ideal:
+                    raise NotImplementedError("specialize=True: view_size=%d, view_tile_size=%d: %s"
+                                              % (g.view_size, g.tile_size, info.reason.decode()))
+            else:
+                N.check(rc)
+                g.spec[want] = h
+        return g.spec[want]
+
+    def _release_spec(self):
+        """unload every handle (the tables changed: the instantiations were compiled for the old ones' LDS layout; or the env goes)"""
+        for g in getattr(self, "_groups", ()):
+            for h in g.spec.values():
+                if h:
+                    self._lib.mg_render_spec_release(h)
+            g.spec, g.spec_info = {}, {}
+
+    def __del__(self):
+        try:
+            self._release_spec()
+        except Exception:      # (interpreter shutdown: the library or the device may be gone already)
+            pass
 
     @property
     def action_space(self):
@@ -1223,6 +1290,14 @@ class MultiGridEnv(object):
             # of the others'
             cfg.atlas_gather_off = 0
             name0 = N.render_kernel_name(cfg)[0] if raster_fits else ""
+            # specialize: the group's plain instantiation is asked for now (nothing of cfg that lives on the device is looked at);
+            # the atlas upload below follows the name of the kernel that will be launched
+            for h in g.spec.values():
+                if h:
+                    self._lib.mg_render_spec_release(h)
+            g.spec, g.spec_info, g.cfg = {}, {}, cfg
+            if raster_fits and self._spec(g, N.WANT_PLAIN):
+                name0 = g.spec_info[N.WANT_PLAIN]["kernel_name"]
             if name0.endswith(", 2>") and not os.environ.get("MG_NO_GATHER_ATLAS"):
                 ts, seg = g.tile_size, 3 * g.tile_size
                 rs = (16 + seg + 3) // 4 * 4
@@ -1246,7 +1321,10 @@ class MultiGridEnv(object):
                 g.kernel_name = "mg::encode_views_kernel<%d>" % (g.view_size if g.view_size in (5, 7, 9) else 0)
             else:
                 g.kernel_name, generic = N.render_kernel_name(cfg)
-                _warn_generic_kernel(g, generic, bool(cfg.prestige_mask))
+                if g.spec.get(N.WANT_PLAIN):
+                    g.kernel_name = g.spec_info[N.WANT_PLAIN]["kernel_name"]
+                else:
+                    _warn_generic_kernel(g, generic, bool(cfg.prestige_mask))
         g0 = self._groups[0]
         self._cfg, self.atlas, self._obj_dev, self._atlas_dev = g0.cfg, g0.atlas, g0.obj_dev, g0.atlas_dev
         self._tables_version = self.obj_reg.version
@@ -1400,7 +1478,10 @@ class MultiGridEnv(object):
             rc = (L.mg_step_encode_views if ep is None else L.mg_step_encode_views_ep)(*head, self.obs.data_ptr(), *tail)
         elif fused and ep is not None:
             # (there is no _ep twin of mg_step_render_encode: encode_in_step takes mg_step_render_ep + mg_encode)
-            if self._ep_fused:
+            h = self._spec(self._groups[0], N.WANT_EPISODE)
+            if h:
+                rc = L.mg_step_render_spec(h, *head, self.obs.data_ptr(), None, ep, stream)
+            elif self._ep_fused:
                 rc = L.mg_step_render_ep(*head, self.obs.data_ptr(), *tail)
                 if rc == N.E_UNSUPPORTED:
                     self._ep_fused, rc = False, None
@@ -1408,12 +1489,22 @@ class MultiGridEnv(object):
             # the whole step — action loop, reset of finished episodes, observation raster — is ONE launch: the wave that
             # renders an env steps it first; with encode_in_step it writes MultiGrid.encode of its envs too, unless there are
             # more than 256 object ids + agent marks, or the grid is read in place, ...
-            if self.encode_in_step and self._enc_fused:
+            # (specialize: through the group's own instantiation where it has one — with the encode: asked for at the first such step)
+            h = self._spec(self._groups[0], N.WANT_ENCODE) if self.encode_in_step else None
+            if h:
+                rc = L.mg_step_render_spec(h, *head, self.obs.data_ptr(), self._encoding_buffer().data_ptr(), None, stream)
+                encoding_written = True
+            elif self.encode_in_step and self._enc_fused:
                 rc = L.mg_step_render_encode(*head, self.obs.data_ptr(), self._encoding_buffer().data_ptr(), stream)
                 self._enc_fused = encoding_written = rc != N.E_UNSUPPORTED
             if not encoding_written:
-                rc = self._launch_step_delta(head, stream)
-                if rc is None:
+                h = self._spec(self._groups[0], N.WANT_PLAIN)
+                rc = None
+                if h is None or self.obs_delta is True:      # (obs_delta keeps the table's path: its one shape is on the table)
+                    rc = self._launch_step_delta(head, stream)
+                if rc is None and h:
+                    rc = L.mg_step_render_spec(h, *head, self.obs.data_ptr(), None, None, stream)
+                elif rc is None:
                     rc = L.mg_step_render(*head, self.obs.data_ptr(), stream)
         if rc is not None:
             N.check(rc)
@@ -1468,6 +1559,8 @@ class MultiGridEnv(object):
         for g in self._groups:
             if self._encoded and not pixels:
                 N.check(self._lib.mg_encode_views(C.byref(g.cfg), st, g.obs.data_ptr(), stream))
+            elif self._spec(g, N.WANT_PLAIN):
+                N.check(self._lib.mg_render_obs_spec(g.spec[N.WANT_PLAIN], C.byref(g.cfg), st, self._pixel_buffer(g).data_ptr(), stream))
             else:
                 N.check(self._lib.mg_render_obs(C.byref(g.cfg), st, self._pixel_buffer(g).data_ptr(), None, None, None, stream))
 

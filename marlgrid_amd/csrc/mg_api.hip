@@ -165,15 +165,10 @@ int32_t mg_render_obs(const MgConfig* cfg, const MgState* st, uint8_t* obs, uint
     return rc(mg::launch_render(*cfg, *st, obs, view_cells, view_agent, vis_mask, (hipStream_t)stream));
 }
 
-static int32_t step_render(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
-                           const MgGenProgram* auto_reset, uint8_t* obs, uint8_t* encode_out, void* stream,
-                           const MgEpisode* ep = nullptr, uint16_t* sig = nullptr, uint32_t sig_flags = 0) {
-    const int e = check_step_args(cfg, st, actions, action_bytes, rewards, auto_reset, ep, true);
-    if (e) return e;
-    if (!obs) return MG_E_ARG;      // (every check between the state's and this one answers MG_E_ARG too)
-    mg::RenderPick pick;
-    if ((encode_out || ep) && !mg::render_pick(*cfg, ep ? mg::kEpisode : mg::kEncode, &pick)) return MG_E_UNSUPPORTED;
-    if (sig && !mg::render_pick(*cfg, mg::kDelta, &pick)) return MG_E_UNSUPPORTED;
+// what the obs kernel's fused step is told (the table's launcher and a specialised handle's alike)
+static mg::FusedStep fused_step_of(const MgConfig* cfg, const void* actions, int32_t action_bytes, float* rewards,
+                                   const MgGenProgram* auto_reset, uint8_t* encode_out, const MgEpisode* ep, uint16_t* sig,
+                                   uint32_t sig_flags) {
     mg::FusedStep fs{};
     fs.actions = actions;
     fs.rewards = rewards;
@@ -189,7 +184,40 @@ static int32_t step_render(const MgConfig* cfg, const MgState* st, const void* a
     if (ep) fs.ep = *ep;
     fs.sig = sig;
     fs.sig_force = (sig_flags & MG_DELTA_FORCE) ? 1 : 0;
+    return fs;
+}
+
+static int32_t step_render(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
+                           const MgGenProgram* auto_reset, uint8_t* obs, uint8_t* encode_out, void* stream,
+                           const MgEpisode* ep = nullptr, uint16_t* sig = nullptr, uint32_t sig_flags = 0) {
+    const int e = check_step_args(cfg, st, actions, action_bytes, rewards, auto_reset, ep, true);
+    if (e) return e;
+    if (!obs) return MG_E_ARG;      // (every check between the state's and this one answers MG_E_ARG too)
+    mg::RenderPick pick;
+    if ((encode_out || ep) && !mg::render_pick(*cfg, ep ? mg::kEpisode : mg::kEncode, &pick)) return MG_E_UNSUPPORTED;
+    if (sig && !mg::render_pick(*cfg, mg::kDelta, &pick)) return MG_E_UNSUPPORTED;
+    const mg::FusedStep fs = fused_step_of(cfg, actions, action_bytes, rewards, auto_reset, encode_out, ep, sig, sig_flags);
     return rc(mg::launch_render(*cfg, *st, obs, nullptr, nullptr, nullptr, (hipStream_t)stream, &fs));
+}
+
+// ... and through an instantiation compiled at run time (mg_rtc.hip: mg_render_specialize)
+int32_t mg_step_render_spec(void* handle, const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes,
+                            float* rewards, const MgGenProgram* auto_reset, uint8_t* obs, uint8_t* encode_out,
+                            const MgEpisode* ep, void* stream) {
+    if (!handle || (encode_out && ep)) return MG_E_ARG;
+    const int e = check_step_args(cfg, st, actions, action_bytes, rewards, auto_reset, ep, true);
+    if (e) return e;
+    if (!obs) return MG_E_ARG;
+    const mg::FusedStep fs = fused_step_of(cfg, actions, action_bytes, rewards, auto_reset, encode_out, ep, nullptr, 0);
+    return mg::launch_render_spec(handle, *cfg, *st, obs, (hipStream_t)stream, &fs);
+}
+
+int32_t mg_render_obs_spec(void* handle, const MgConfig* cfg, const MgState* st, uint8_t* obs, void* stream) {
+    if (!handle) return MG_E_ARG;
+    const int e = check_both(cfg, st);
+    if (e) return e;
+    if (!obs) return MG_E_ARG;
+    return mg::launch_render_spec(handle, *cfg, *st, obs, (hipStream_t)stream, nullptr);
 }
 
 int32_t mg_step_render(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,

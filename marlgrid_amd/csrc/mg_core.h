@@ -9,8 +9,10 @@
 // and 1 on the host).
 #pragma once
 
+#if !defined(__HIPCC_RTC__)   // (a run-time compile — mg_rtc.hip — has no system headers: its source supplies these names)
 #include <math.h>
 #include <stdint.h>
+#endif
 
 #include "marlgrid_hip.h"
 #include "mg_step_layout.h"

@@ -3,8 +3,10 @@
 // Written for CDNA4 only (wave64, 160 KiB LDS/CU); no portability layer.
 #pragma once
 
+#if !defined(__HIPCC_RTC__)   // (a run-time compile — mg_rtc.hip — has no system headers: its source supplies these names)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#endif
 
 #include "marlgrid_hip.h"
 #include "mg_core.h"

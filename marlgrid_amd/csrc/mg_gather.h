@@ -30,9 +30,12 @@
 // arithmetic is checked on the host against a byte-by-byte raster; the product never loads that build).
 #pragma once
 
+#if !defined(__HIPCC_RTC__)   // (a run-time compile — mg_rtc.hip — has no system headers: its source supplies these names)
 #include <stdint.h>
+#endif
 
 #include "mg_core.h"
+#include "mg_render_pick.h"   // gather_gcd, gather_pick_c, gather_trips
 
 // (host harness: tests/native defines this to check every LDS offset the raster forms against the buffers' sizes)
 #if !defined(MG_GATHER_BOUNDS)
@@ -49,8 +52,6 @@ MG_HD uint32_t gather_align(uint32_t hi, uint32_t lo, uint32_t sh) {   // bytes 
 #endif
 }
 
-constexpr int gather_gcd(int a, int b) { return b ? gather_gcd(b, a % b) : a; }
-
 // geometry of one (view size, tile size)
 template <int VS, int TS>
 struct GatherGeom {
@@ -62,22 +63,10 @@ struct GatherGeom {
     static constexpr int TAIL = 32;                               // zero bytes behind the last row of the atlas
     static constexpr int G16 = gather_gcd(16, RB);
     static constexpr int PC = RB / G16, PR = 16 / G16;            // chunks / pixel rows per period
-    // a CYCLE of C periods = NT <= 4 trips (= sets of lane constants): the C whose trips are best filled, whole bands of
-    // tiles (C * PR a multiple of TS: the tile row of a lane's segment is then a constant of the set — a quarter fewer
-    // instructions per window) counting for 1.3; ties: the smaller C
-    static constexpr int pick_c() {
-        int best = 1, best_score = 0;
-        for (int c = 1; c <= 8; c++) {
-            const int cc = c * PC, nt = (cc + 63) / 64;
-            if (nt > 4) continue;
-            const int score = cc * 1000 / (nt * 64) * (((c * PR) % TS == 0) ? 13 : 10);
-            if (score > best_score) { best = c; best_score = score; }
-        }
-        return best;
-    }
-    static constexpr int C = pick_c();
+    // a CYCLE of C periods = NT <= 4 trips (= sets of lane constants): gather_pick_c (mg_render_pick.h, where the pick asks too)
+    static constexpr int C = gather_pick_c(PC, PR, TS);
     static constexpr int CC = C * PC;                             // chunks per cycle
-    static constexpr int NT = (CC + 63) / 64;                     // trips (= sets of lane constants) per cycle
+    static constexpr int NT = gather_trips(VS, TS);               // trips (= sets of lane constants) per cycle: (CC + 63) / 64
     static_assert(NT <= 4, "too many sets of lane constants");
     static constexpr int LPT = (CC + NT - 1) / NT;                // lanes of a trip (the last trip of a cycle may have fewer)
     static constexpr int CYC_ROWS = C * PR;                       // pixel rows per cycle

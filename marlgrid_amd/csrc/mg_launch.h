@@ -15,6 +15,9 @@ struct FusedStep;
 // (which instantiation a configuration gets, whether it has one with the encode / the episode code, its LDS: mg_render_pick.h)
 hipError_t launch_render(const MgConfig& cfg, const MgState& st, uint8_t* obs, uint8_t* view_cells,
                          uint8_t* view_agent, uint8_t* vis_mask, hipStream_t s, const FusedStep* fused_step = nullptr);
+// ... through a handle of mg_render_specialize (mg_rtc.hip); answers an MG_* code: MG_E_ARG when the handle was made for another shape
+int32_t launch_render_spec(void* handle, const MgConfig& cfg, const MgState& st, uint8_t* obs, hipStream_t s,
+                           const FusedStep* fused_step);
 hipError_t launch_encode(const MgConfig& cfg, const MgState& st, const uint8_t* vis_mask, uint8_t* out,
                          hipStream_t s);
 // every agent's gen_obs_grid -> encode (mg_encode_views.hip): out uint8 [B][nv][vs][vs][3]

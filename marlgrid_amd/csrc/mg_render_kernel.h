@@ -29,9 +29,15 @@
 //     envs of the wave's run) are carried over in the buffer, so everything but the first and last
 //     <16 bytes of a wave's whole run leaves as aligned 16-byte stores.
 // No MFMA: there is no contraction anywhere in this path.
+//
+// This header is also what a run-time compile reads (mg_rtc.hip: mg_render_specialize hands it to hipRTC, which defines
+// __HIPCC_RTC__ and has no system headers): under that macro the #includes of system headers and the launcher's half at the
+// end are skipped, and MG_RTC_LDS_BYTES, when given, is the workgroup's LDS as a static array.
 #pragma once
 #include "mg_device.h"
+#if !defined(__HIPCC_RTC__)
 #include "mg_launch.h"
+#endif
 #if defined(MG_AB_VARIANTS)
 #include <stdlib.h>   // getenv: the measurement build only (libmarlgrid_hip_ab.so, loaded by tools/)
 #endif
@@ -80,6 +86,15 @@ __device__ __forceinline__ void or_segment(const uint8_t* __restrict__ sb, uint3
         lo = w[CH];
     }
 }
+
+// 16 bytes on their way from the piece buffer to HBM (the assemble-and-stream raster's ds_read_b128 -> global_store_dwordx4).
+// hipRTC's uint4 is a class of its own headers whose four in-flight copies the compiler leaves behind as stores to a private
+// array nobody reads — scratch traffic in the middle of the store run —: a run-time compile (mg_rtc.hip) takes the plain vector.
+#if defined(__HIPCC_RTC__)
+typedef uint32_t StreamChunk __attribute__((ext_vector_type(4)));
+#else
+typedef uint4 StreamChunk;
+#endif
 
 // A second look at a by-value kernel parameter, through a pointer the compiler cannot see through: the loads
 // stay where the values are used (scalar loads from the kernarg segment) instead of being hoisted to the kernel's
@@ -267,7 +282,11 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
     constexpr bool kEnc = (VX_ & 16) != 0;      // + 16: mg_step_render_encode
     constexpr bool kEp = (VX_ & 32) != 0;       // + 32: mg_step_render_ep — reset mode and episode outputs (MgEpisode) in the fused step
     constexpr bool kDelta = (VX_ & 64) != 0;    // + 64: mg_step_render_delta — bands whose tiles equal the recorded signature are not stored
+#if defined(MG_RTC_LDS_BYTES)      // a run-time compile for ONE configuration (mg_rtc.hip) whose workgroup takes more than 64 KiB: the size compiled in
+    __shared__ __attribute__((aligned(16))) uint8_t smem[MG_RTC_LDS_BYTES];
+#else
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+#endif
     // the wave index is uniform: told to the compiler, everything derived from it (the wave's scratch
     // pointers, its run of envs, loop bounds) lives in SGPRs instead of one VGPR each
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1418,11 +1437,11 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                         head = 0;
                         c0 = 1;
                     }
-                    const uint4* src16 = reinterpret_cast<const uint4*>(w_out);
-                    uint4* dst16 = reinterpret_cast<uint4*>(out_base);
+                    const StreamChunk* src16 = reinterpret_cast<const StreamChunk*>(w_out);
+                    StreamChunk* dst16 = reinterpret_cast<StreamChunk*>(out_base);
                     uint32_t c = c0 + (uint32_t)lane;
                     for (; c + 3u * kWave < full; c += 4u * kWave) {
-                        const uint4 v0 = src16[c], v1 = src16[c + kWave], v2 = src16[c + 2 * kWave], v3 = src16[c + 3 * kWave];
+                        const StreamChunk v0 = src16[c], v1 = src16[c + kWave], v2 = src16[c + 2 * kWave], v3 = src16[c + 3 * kWave];
                         dst16[c] = v0; dst16[c + kWave] = v1; dst16[c + 2 * kWave] = v2; dst16[c + 3 * kWave] = v3;
                     }
                     for (; c < full; c += kWave) dst16[c] = src16[c];
@@ -1455,6 +1474,7 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
 }
 
 
+#if !defined(__HIPCC_RTC__)      // the launcher's half: host code (a run-time compile — mg_rtc.hip — takes the kernel alone)
 // Compute units of the current device (256 on a whole MI355X; 32 per partition in CPX mode): what the persistent
 // grid is sized for.  Asked once per device (hipDeviceGetAttribute is a host-side table look-up, no stream work).
 inline int device_cus() {
@@ -1469,31 +1489,25 @@ inline int device_cus() {
     return cached[dev];
 }
 
-// One launch of instantiation <VS_, TS_, WPB, VX_, RM_>; `lds`: its workgroup's dynamic LDS (render_lds_bytes — the launcher's pick)
-template <int VS_, int TS_, int WPB, int VX_ = 0, int RM_ = 0>
-hipError_t launch_render_t(const MgConfig& cfg, const MgState& st, uint8_t* obs, uint8_t* c, uint8_t* a,
-                                  uint8_t* v, hipStream_t s, const FusedStep& fs, size_t lds) {
-    static_assert(RM_ == 1 || TS_ == 0 || (TS_ % 8) != 0 || TS_ == 8 || TS_ == 16 || TS_ == 32, "see render_chunk_raster");
-    const RenderScratch L = render_scratch_for(cfg, WPB, RM_);
-    constexpr int V_ = VX_ & 15;
-    const size_t atlas_lds = (V_ == 8 || V_ == 12) ? 0 : (size_t)render_atlas_lds_bytes(cfg, RM_);
+// What a launch of instantiation <., ., wpb, vx, rm> with `lds` bytes of LDS per workgroup passes besides the caller's
+// arguments: the workgroups of its persistent grid (the return value) and the launch constants.  One text for the table's
+// launcher below and for the run-time-compiled instantiations (mg_rtc.hip).
+inline int render_launch_plan(const MgConfig& cfg, int wpb, int vx, int rm, size_t lds, RenderLaunch* out) {
+    const RenderScratch L = render_scratch_for(cfg, wpb, rm);
+    const int V_ = vx & 15;
+    const size_t atlas_lds = (V_ == 8 || V_ == 12) ? 0 : (size_t)render_atlas_lds_bytes(cfg, rm);
     const RenderShared sh = render_shared_layout(cfg);
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&render_kernel<VS_, TS_, WPB, VX_, RM_>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
     // Persistent grid: at most the workgroups that are co-resident on the device's CUs (each stages the atlas
     // once), sized so that every wave walks the same number of envs (an uneven tail costs up to one
     // env-time in ~6).  Registers (~87 VGPRs) admit 5 waves per SIMD = 20 per CU.
     int per_cu = (int)((160 * 1024) / (lds ? lds : 1));
-    if (per_cu > 20 / WPB) per_cu = 20 / WPB;
+    if (per_cu > 20 / wpb) per_cu = 20 / wpb;
 #if defined(MG_AB_VARIANTS)
     if (const char* f = getenv("MG_RENDER_PER_CU")) { const int v = atoi(f); if (v >= 1 && v < per_cu) per_cu = v; }
 #endif
     if (per_cu < 1) per_cu = 1;
     const int max_blocks = device_cus() * per_cu;
-    const int need = (cfg.B + WPB - 1) / WPB;   // workgroups if every wave took one env
+    const int need = (cfg.B + wpb - 1) / wpb;   // workgroups if every wave took one env
     const int rounds = (need + max_blocks - 1) / max_blocks;
     int blocks = (need + rounds - 1) / rounds;
 #if defined(MG_AB_VARIANTS)
@@ -1503,7 +1517,7 @@ hipError_t launch_render_t(const MgConfig& cfg, const MgState& st, uint8_t* obs,
 #endif
     RenderLaunch lc;
     lc.L = L;
-    lc.per_wave = (cfg.B + blocks * WPB - 1) / (blocks * WPB);
+    lc.per_wave = (cfg.B + blocks * wpb - 1) / (blocks * wpb);
     const uint32_t nv = (uint32_t)(cfg.n_view ? cfg.n_view : cfg.n_agents), vs = (uint32_t)cfg.view_size;
     lc.m_n = Div20((uint32_t)cfg.n_agents).m;
     lc.m_nv = Div20(nv).m;
@@ -1516,10 +1530,24 @@ hipError_t launch_render_t(const MgConfig& cfg, const MgState& st, uint8_t* obs,
     lc.sh = sh;
 #if defined(MG_AB_VARIANTS)
     lc.stamps = g_ab_stamps;
-#endif
-#if defined(MG_AB_VARIANTS)
     if (const char* f = getenv("MG_RENDER_DEPTH")) lc.depth_mode = atoi(f);   // 1: every wave view -> raster env by env
 #endif
+    *out = lc;
+    return blocks;
+}
+
+// One launch of instantiation <VS_, TS_, WPB, VX_, RM_>; `lds`: its workgroup's dynamic LDS (render_lds_bytes — the launcher's pick)
+template <int VS_, int TS_, int WPB, int VX_ = 0, int RM_ = 0>
+hipError_t launch_render_t(const MgConfig& cfg, const MgState& st, uint8_t* obs, uint8_t* c, uint8_t* a,
+                                  uint8_t* v, hipStream_t s, const FusedStep& fs, size_t lds) {
+    static_assert(RM_ == 1 || TS_ == 0 || (TS_ % 8) != 0 || TS_ == 8 || TS_ == 16 || TS_ == 32, "see render_chunk_raster");
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&render_kernel<VS_, TS_, WPB, VX_, RM_>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    RenderLaunch lc;
+    const int blocks = render_launch_plan(cfg, WPB, VX_, RM_, lds, &lc);
     hipLaunchKernelGGL((render_kernel<VS_, TS_, WPB, VX_, RM_>), dim3(blocks), dim3(WPB * 64), lds, s, cfg, st, obs, c, a, v,
                        lc, fs);
     return hipGetLastError();
@@ -1532,5 +1560,6 @@ hipError_t launch_render_t(const MgConfig& cfg, const MgState& st, uint8_t* obs,
 #define MG_RENDER_INSTANTIATE(VS, TS, WPB, V, RM)                                                                          \
     template hipError_t launch_render_t<VS, TS, WPB, V, RM>(const MgConfig&, const MgState&, uint8_t*, uint8_t*, uint8_t*,  \
                                                           uint8_t*, hipStream_t, const FusedStep&, size_t);
+#endif   // !__HIPCC_RTC__
 
 }  // namespace mg

@@ -4,8 +4,10 @@
 // tests (tests/native) read the same rules.  No environment, no globals, no HIP call.
 #pragma once
 
+#if !defined(__HIPCC_RTC__)   // (a run-time compile — mg_rtc.hip — has no system headers: its source supplies these names)
 #include <stddef.h>
 #include <stdint.h>
+#endif
 
 #include "marlgrid_hip.h"
 #include "mg_step_layout.h"   // MG_LAYOUT_FN (the layout functions: the kernels call them too) and the fused step's columns
@@ -65,6 +67,27 @@ MG_LAYOUT_FN bool render_gather(const MgConfig& cfg) {
     return (vs == 3 || vs == 4 || vs == 5 || vs == 6 || vs == 8 || vs == 9 || vs == 11 || vs == 13 || vs == 15) && ts == 5 && cfg.prestige_mask == 0;
 }
 MG_LAYOUT_FN int render_gather_row_bytes(int ts) { return (16 + 3 * ts + 3) / 4 * 4; }
+// The gather raster's cycle (mg_gather.h: GatherGeom takes its C and NT from here; render_pick_ideal asks at run time whether a
+// (view, tile) pair has one).  A pixel row is RB = 3 * vs * ts bytes; the pattern of 16-byte chunks over rows repeats every
+// PC = RB / gcd(16, RB) chunks = PR = 16 / gcd(16, RB) rows.  A CYCLE of C periods = NT <= 4 trips (= sets of lane constants):
+// the C whose trips are best filled, whole bands of tiles (C * PR a multiple of TS: the tile row of a lane's segment is then a
+// constant of the set — a quarter fewer instructions per window) counting for 1.3; ties: the smaller C.
+constexpr int gather_gcd(int a, int b) { return b ? gather_gcd(b, a % b) : a; }
+constexpr int gather_pick_c(int pc, int pr, int ts) {
+    int best = 1, best_score = 0;
+    for (int c = 1; c <= 8; c++) {
+        const int cc = c * pc, nt = (cc + 63) / 64;
+        if (nt > 4) continue;
+        const int score = cc * 1000 / (nt * 64) * (((c * pr) % ts == 0) ? 13 : 10);
+        if (score > best_score) { best = c; best_score = score; }
+    }
+    return best;
+}
+// trips per cycle (GatherGeom::NT); more than 4 — a period of more than 256 chunks — is a shape the gather raster does not take
+constexpr int gather_trips(int vs, int ts) {
+    const int rb = 3 * vs * ts, g = gather_gcd(16, rb);
+    return (gather_pick_c(rb / g, 16 / g, ts) * (rb / g) + 63) / 64;
+}
 MG_LAYOUT_FN int render_atlas_raw_bytes(const MgConfig& cfg) {
     return (4 * cfg.n_tiles * cfg.tile_size * cfg.tile_size * 3 + 15) / 16 * 16;
 }
@@ -306,6 +329,44 @@ inline bool render_pick(const MgConfig& cfg, RenderWant want, RenderPick* out) {
     }
     if (lds > kRenderLdsMax) return false;
     p.lds = (int)lds;
+    *out = p;
+    return true;
+}
+
+// ---- the pick if any instantiation could be made (mg_rtc.hip: mg_render_specialize compiles it at run time) ---------------------
+// Which instantiation the configuration would get if its view and tile size were compiled in; false: nothing to gain, the
+// table's answer stays.  Only the three raster families of the table, with new values:
+//   gather              <vs, ts, W, V, 2>  ts >= 5, ts % 8 != 0, a cycle of at most 4 trips (gather_trips), the padded atlas in LDS
+//   chunk               <vs, ts, W, V, 0>  ts 8, 16, 32
+//   assemble-and-stream <vs, 0, W, V, 0>   everything else (a compile-time tile size off the chunk sizes is no family of the table)
+// W: 4 under 4096 envs, else 16 for views up to 9 and 8 above (larger views' shadow-cast arrays need more than 128 VGPRs), stepped
+// down 16 -> 8 -> 4 while the workgroup does not fit LDS.  V: + 16 (kEncode, under render_pick's own conditions: a table for every
+// grid byte value that fits beside four waves of scratch) or + 32 (kEpisode).  Not specialised: a grid read in place, 'prestige'
+// agents, an atlas in global memory (every V != 0 of the table), kDelta, views under 3 — and a shape the table already has compiled in
+// (its view and the family's tile size: a hand-picked entry, whatever its workgroup, is never replaced).
+inline bool render_pick_ideal(const MgConfig& cfg, RenderWant want, RenderPick* out) {
+    const int vs = cfg.view_size, ts = cfg.tile_size;
+    RenderPick plain;
+    if (want == kDelta || vs < 3 || vs > MG_MAX_VIEW || !render_pick(cfg, kPlain, &plain) || plain.v != 0) return false;
+    RenderPick p = {vs, 0, 4, 0, 0, 0};
+    if (ts >= 5 && ts % 8 != 0 && gather_trips(vs, ts) <= 4 && render_fits(cfg, 4, 2)) { p.ts = ts; p.rm = 2; }
+    else if (!render_fits(cfg, 4, 0)) return false;
+    else if (ts == 8 || ts == 16 || ts == 32) p.ts = ts;
+    int enc_ne = 0;
+    if (want == kEncode) {
+        enc_ne = render_enc_entries(cfg);
+        if (enc_ne == 0 || render_lds_bytes(cfg, 4, p.rm, 0, enc_ne) > kRenderLdsMax) return false;
+        p.v = 16;
+    } else if (want == kEpisode) {
+        p.v = 32;
+    }
+    p.wpb = cfg.B < 4096 ? 4 : vs <= 9 ? 16 : 8;
+    while (p.wpb > 4 && render_lds_bytes(cfg, p.wpb, p.rm, p.v, enc_ne) > kRenderLdsMax) p.wpb >>= 1;
+    const size_t lds = render_lds_bytes(cfg, p.wpb, p.rm, p.v, enc_ne);
+    if (lds > kRenderLdsMax) return false;
+    p.lds = (int)lds;
+    RenderPick t;
+    if (render_pick(cfg, want, &t) && t.vs == p.vs && t.ts == p.ts && t.v == p.v && t.rm == p.rm) return false;
     *out = p;
     return true;
 }

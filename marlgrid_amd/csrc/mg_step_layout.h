@@ -3,8 +3,10 @@
 // tests/native, which runs the step bodies on buffers of exactly these sizes.  Plain C++17 behind marlgrid_hip.h.
 #pragma once
 
+#if !defined(__HIPCC_RTC__)   // (a run-time compile — mg_rtc.hip — has no system headers: its source supplies these names)
 #include <stddef.h>
 #include <stdint.h>
+#endif
 
 #include "marlgrid_hip.h"
 

@@ -72,6 +72,11 @@ extern "C" {
 #define MG_MAX_AGENTS 32  /* agents per env (the reference: any number, base.py:335-369; register_marl_env asserts <= 6) */
 #define MG_MAX_OBJ 256    /* object kinds incl. id 0 = None: the ids are uint8, as the reference's registry keys are (base.py:25,91) */
 #define MG_MAX_GEN 1024   /* ops of a reset program (device memory: a sanity bound, not a buffer size) */
+/* `_rand_int` draws of a reset program (MgGenOp below) */
+#define MG_GEN_DRAWS 8            /* draw registers per program: draw r lives in byte r of one 64-bit scalar during the reset */
+#define MG_GEN_SYM 0x40000000     /* an operand x0/y0/x1/y1 with this bit is `const +- draw[r]`, not a plain integer: */
+#define MG_GEN_NEG 0x20000000     /*   set: const - draw[r]; clear: const + draw[r] */
+#define MG_GEN_DRAW_SHIFT 16      /*   r = (operand >> 16) & 7; const = (int16_t)(operand & 0xFFFF) */
 #define MG_MAX_VIEW 31    /* view_size (agents.py:19-35: any; a view row is a 32-bit mask here) */
 #define MG_KEY_WORDS 2
 #define MG_MT_N 624
@@ -207,9 +212,18 @@ typedef struct MgGenOp {
                                    * max_tries == 0 (ABI 4): a STATIC edit that `_gen_grid` makes after a random placement
                                    * (put_obj / grid.set / a wall helper, base.py:655-662, 160-176): `obj` (0 = None) is
                                    * written into every cell of [x0,x1) x [y0,y1), replacing what is there; no RNG draw.
-                                   * Static edits BEFORE the first placement are part of template_grid. */
+                                   * Static edits BEFORE the first placement are part of template_grid.
+                                   * max_tries < 0: a DRAW, `self._rand_int(x0, x1)` inside `_gen_grid`: draw[obj] = x0 +
+                                   * bounded(x1 - x0 - 1) on the env's RNG (numpy's randint: masked rejection; a one-value
+                                   * range consumes nothing), obj in [0, MG_GEN_DRAWS); count, y0, y1 and reject are unused.
+                                   * The draws live for the duration of ONE reset; they are no part of MgState. */
     int32_t x0, y0, x1, y1;       /* sampling rectangle [x0,x1) x [y0,y1): place_obj(top=, size=) clamped
-                                   * to the grid (base.py:692-695); the whole grid by default */
+                                   * to the grid (base.py:692-695); the whole grid by default.  Each of the four is a plain
+                                   * integer or, with MG_GEN_SYM, `const +- draw[r]` of an EARLIER draw op — evaluated per env
+                                   * when the op runs (a draw's own x0 / x1 as well).  A place or fill rectangle with such an
+                                   * operand is clamped to the grid on the device (for a place op that is the reference's
+                                   * clamp); a place op whose clamped rectangle is empty records MG_ERR_VALUE (randint with
+                                   * low >= high).  The values a draw can take must lie in 0..255. */
     int32_t reject;               /* place_obj(reject_fn=) (base.py:690, 700-701): the callback tabulated once over the
                                    * grid — row `reject` of MgGenProgram.reject, -1 = none.  A per-draw Python callback
                                    * cannot run on the device; a function of the position alone is a table. */
@@ -220,8 +234,8 @@ typedef struct MgGenProgram {
     const MgGenOp* ops;           /* DEVICE, [n_ops]: placements and late static edits, in `_gen_grid` order — upstream's `_gen_grid`
                                    * is free Python of any length (marlgrid/envs); the program lives in device memory, not in the
                                    * launch arguments.  The library cannot look into it from the host: the caller hands over ops
-                                   * with 0 <= obj < n_obj (>= 1 for placements), a non-empty rectangle inside the grid, count >= 0,
-                                   * max_tries >= 0 and reject in [-1, n_reject) */
+                                   * with 0 <= obj < n_obj (>= 1 for placements), count >= 0 and reject in [-1, n_reject); a rectangle
+                                   * of plain integers is non-empty and inside the grid (one with a draw operand is clamped) */
     const uint8_t* reject;        /* device, [n_reject][cells_stride], index x*H + y, != 0 = rejected; NULL if no op
                                    * has a reject table */
     int32_t n_reject;

@@ -9,6 +9,8 @@ import os
 
 MAX_AGENTS, MAX_OBJ, MAX_GEN, MAX_VIEW, KEY_WORDS, MT_N, MT_HEAD = 32, 256, 1024, 31, 2, 624, 16
 ABI_VERSION = 6
+# `_rand_int` draws of a reset program (MG_GEN_* in the C header): an operand with GEN_SYM is `const +- draw[r]`
+GEN_DRAWS, GEN_SYM, GEN_NEG, GEN_DRAW_SHIFT = 8, 0x40000000, 0x20000000, 16
 
 OK = 0
 ERR_VALUE, ERR_RECURSION, ERR_TYPE, ERR_ASSERT, ERR_ATTRIBUTE = 1, 2, 3, 4, 5

@@ -58,6 +58,72 @@ def _on_device(fn):
     return wrapper
 
 
+_NO_BRANCH = ("a value of self._rand_int(...) inside _gen_grid is drawn later, per env, on the device: _gen_grid may compute "
+              "with it (draw + k, k + draw, draw - k, k - draw with Python ints) and hand the result to put_obj / grid.set / the "
+              "wall helpers / place_obj(top=, size=) / a later _rand_int, but it cannot branch on it (%s)")
+
+
+class GenDraw(object):
+    """What `self._rand_int(lo, hi)` returns while `_gen_grid` is recorded: `const + sign * draw[reg]`, sign +-1 — a
+    coordinate or extent whose value every env draws for itself at every reset (MgGenOp, MG_GEN_SYM)."""
+    __slots__ = ("reg", "sign", "const")
+    __hash__ = None
+
+    def __init__(self, reg, sign=1, const=0):
+        self.reg, self.sign, self.const = reg, sign, const
+
+    @staticmethod
+    def _int(k, what):
+        if isinstance(k, (bool, GenDraw)) or not isinstance(k, (int, np.integer)):
+            raise NotImplementedError(_NO_BRANCH % what)
+        return int(k)
+
+    def __add__(self, k):
+        return GenDraw(self.reg, self.sign, self.const + self._int(k, "draw + %s" % type(k).__name__))
+    __radd__ = __add__
+
+    def __sub__(self, k):
+        return GenDraw(self.reg, self.sign, self.const - self._int(k, "draw - %s" % type(k).__name__))
+
+    def __rsub__(self, k):
+        return GenDraw(self.reg, -self.sign, self._int(k, "%s - draw" % type(k).__name__) - self.const)
+
+    def _refuse(name):
+        def f(self, *a, **k):
+            raise NotImplementedError(_NO_BRANCH % name)
+        return f
+    for _n in ("eq", "ne", "lt", "le", "gt", "ge", "bool", "int", "index", "float", "mul", "rmul", "floordiv", "rfloordiv",
+               "truediv", "rtruediv", "mod", "rmod", "neg", "pos", "abs", "pow", "rpow", "lshift", "rshift", "and", "or",
+               "xor", "invert", "round", "trunc"):
+        locals()["__%s__" % _n] = _refuse(_n)
+    del _n, _refuse
+
+    def __repr__(self):
+        return "<%d %s draw[%d]>" % (self.const, "+" if self.sign > 0 else "-", self.reg)
+
+    def encode(self):
+        if not -32768 <= self.const <= 32767:
+            raise NotImplementedError("_gen_grid: a constant of %d next to a draw does not fit the program's operand" % self.const)
+        return N.GEN_SYM | (N.GEN_NEG if self.sign < 0 else 0) | (self.reg << N.GEN_DRAW_SHIFT) | (self.const & 0xFFFF)
+
+
+def _gen_add(a, b):
+    """a + b inside the recorder (top + size, x + length): the two may hold the SAME draw with opposite signs"""
+    if isinstance(a, GenDraw) and isinstance(b, GenDraw):
+        if a.reg == b.reg and a.sign + b.sign == 0:
+            return a.const + b.const
+        raise NotImplementedError(_NO_BRANCH % "a sum of two draws")
+    return a + b
+
+
+def _gen_enc(v):
+    return v.encode() if isinstance(v, GenDraw) else int(v)
+
+
+def _any_draw(*vs):
+    return any(isinstance(v, GenDraw) for v in vs)
+
+
 class ObjectRegistry(object):
     """object kind <-> uint8 id (the reference keeps instance <-> key maps per grid,
     base.py:19-64; here ids index the device object table and are stable for the env's life)."""
@@ -151,9 +217,12 @@ class MultiGrid(object):
 
     # ---- layout recording / live edits --------------------------------------------------------
     def set(self, i, j, obj):
+        env = self._env
+        if env._tracing and _any_draw(i, j):
+            env._tr_fill_sym(self.obj_reg.get_key(obj), [(i, j, _gen_add(i, 1), _gen_add(j, 1))])
+            return
         assert i >= 0 and i < self.width
         assert j >= 0 and j < self.height
-        env = self._env
         if env._tracing:
             key = self.obj_reg.get_key(obj)
             if env._tr_static(("put", key, int(i), int(j)), key, [(int(i), int(j), int(i) + 1, int(j) + 1)]):
@@ -166,20 +235,34 @@ class MultiGrid(object):
     def horz_wall(self, x, y, length=None, obj_type=Wall):
         if length is None:
             length = self.width - x
+        if _any_draw(x, y, length):
+            return self._wall_sym(obj_type, [(x, y, _gen_add(x, length), _gen_add(y, 1))])
         self._wall(("horz_wall", int(x), int(y), int(length)), [(x + i, y) for i in range(length)], obj_type,
                    [(x, y, x + length, y + 1)])
 
     def vert_wall(self, x, y, length=None, obj_type=Wall):
         if length is None:
             length = self.height - y
+        if _any_draw(x, y, length):
+            return self._wall_sym(obj_type, [(x, y, _gen_add(x, 1), _gen_add(y, length))])
         self._wall(("vert_wall", int(x), int(y), int(length)), [(x, y + j) for j in range(length)], obj_type,
                    [(x, y, x + 1, y + length)])
 
     def wall_rect(self, x, y, w, h, obj_type=Wall):
+        if _any_draw(x, y, w, h):
+            xe, ye = _gen_add(x, w), _gen_add(y, h)
+            return self._wall_sym(obj_type, [(x, y, xe, _gen_add(y, 1)), (x, ye - 1, xe, ye), (x, y, _gen_add(x, 1), ye),
+                                             (xe - 1, y, xe, ye)])
         cells = ([(x + i, y) for i in range(w)] + [(x + i, y + h - 1) for i in range(w)]
                  + [(x, y + j) for j in range(h)] + [(x + w - 1, y + j) for j in range(h)])
         self._wall(("wall_rect", int(x), int(y), int(w), int(h)), cells, obj_type,
                    [(x, y, x + w, y + 1), (x, y + h - 1, x + w, y + h), (x, y, x + 1, y + h), (x + w - 1, y, x + w, y + h)])
+
+    def _wall_sym(self, obj_type, rects):
+        """a wall helper with a draw among its arguments: its rectangles as fills of the reset program"""
+        if not self._env._tracing:
+            raise NotImplementedError(_NO_BRANCH % "used outside _gen_grid")
+        self._env._tr_fill_sym(self.obj_reg.get_key(obj_type()), rects)
 
     def _wall(self, sym, cells, obj_type, rects):
         env = self._env
@@ -948,6 +1031,7 @@ class MultiGridEnv(object):
         self._tr_sym = []
         self._tr_ops = []
         self._tr_late = {}          # index into _tr_ops -> the symbolic form of a static edit recorded as op(s)
+        self._tr_draws = []         # per `_rand_int` so far: the (lowest, highest) value it can take, over all earlier draws
 
     def _tr_static(self, sym, key, rects):
         """A static layout edit of `_gen_grid` (grid.set / put_obj / the wall helpers).  Before the first random
@@ -963,7 +1047,7 @@ class MultiGridEnv(object):
             # a fill that continues the one before it (same object, same rows or columns, adjacent) is the same op, larger
             last = self._tr_ops[-1]
             merged = None
-            if last[2] == 0 and last[0] == int(key) and last[7] is None:
+            if last[2] == 0 and last[0] == int(key) and last[7] is None and not any(v & N.GEN_SYM for v in last[3:7]):
                 lx0, ly0, lx1, ly1 = last[3:7]
                 if (ly0, ly1) == (y0, y1) and (lx1 == x0 or x1 == lx0):
                     merged = (int(key), 1, 0, min(lx0, x0), y0, max(lx1, x1), y1, None)
@@ -979,6 +1063,76 @@ class MultiGridEnv(object):
             self._tr_late.setdefault(first, []).extend(sym if isinstance(sym, list) else [sym])
         return False
 
+    def _tr_cases(self, *operands):
+        """every value the operands (ints or GenDraw) can take together, over the static intervals of the draws in them"""
+        import itertools
+        regs = sorted({v.reg for v in operands if isinstance(v, GenDraw)})
+        spans = [range(self._tr_draws[r][0], self._tr_draws[r][1] + 1) for r in regs]
+        for vals in itertools.product(*spans):
+            d = dict(zip(regs, vals))
+            yield tuple(v.const + v.sign * d[v.reg] if isinstance(v, GenDraw) else int(v) for v in operands)
+
+    def _rand_int(self, low, high):
+        """gym-minigrid's `_rand_int`: `self.np_random.randint(low, high)`.  Inside `_gen_grid` the draw is recorded — every
+        env makes it for itself on the device at every reset, from its own RNG, where upstream makes it — and what comes
+        back is a `GenDraw`: usable as a coordinate or extent of later put_obj / grid.set / wall helpers, in place_obj's
+        `top` / `size`, and as a bound of a later `_rand_int`.  Programs whose every possible draw cannot be shown to stay
+        legal (hi > lo here, fills inside the grid, sampling rectangles non-empty) are refused with ValueError when they
+        are recorded; upstream would fail for some seeds only."""
+        if not self._tracing or self._tr_grid is None:
+            raise NotImplementedError(_NO_BRANCH % "_rand_int outside _gen_grid, or before self.grid = MultiGrid(...)")
+        for v in (low, high):
+            if not isinstance(v, GenDraw):
+                GenDraw._int(v, "_rand_int(%s)" % type(v).__name__)
+        if len(self._tr_draws) >= N.GEN_DRAWS:
+            raise NotImplementedError("_gen_grid makes more than %d _rand_int draws: a reset program holds at most %d (MG_GEN_DRAWS: "
+                                      "the draws of a reset live in one 64-bit register)" % (N.GEN_DRAWS, N.GEN_DRAWS))
+        cases = list(self._tr_cases(low, high))
+        if any(hi <= lo for lo, hi in cases):
+            raise ValueError("_rand_int(%r, %r): not high > low for every value the earlier draws can take" % (low, high))
+        vmin, vmax = min(lo for lo, _ in cases), max(hi for _, hi in cases) - 1
+        if vmin < 0 or vmax > 255:
+            raise ValueError("_rand_int(%r, %r) inside _gen_grid: values %d..%d do not fit a grid coordinate (0..255)"
+                             % (low, high, vmin, vmax))
+        reg = len(self._tr_draws)
+        self._tr_draws.append((vmin, vmax))
+        self._tr_ops.append((reg, 1, -1, _gen_enc(low), 0, _gen_enc(high), 0, None))
+        self._tr_late[len(self._tr_ops) - 1] = [("draw", reg, _gen_enc(low), _gen_enc(high))]
+        return GenDraw(reg)
+
+    def _tr_fill_sym(self, key, rects):
+        """A static edit with a draw among its coordinates: one fill op per rectangle, its operands evaluated per env on the
+        device; never merged with its neighbours.  Proved here for every possible draw: non-empty and inside the grid."""
+        g = self._tr_grid
+        for rect in rects:
+            cases = list(self._tr_cases(*rect))
+            if any(not (0 <= x0 < x1 <= self.width and 0 <= y0 < y1 <= self.height) for x0, y0, x1, y1 in cases):
+                raise ValueError("_gen_grid: the edit of cells [%r, %r) x [%r, %r) is not inside the %d x %d grid and non-empty for "
+                                 "every value the draws can take" % (rect[0], rect[2], rect[1], rect[3], self.width, self.height))
+            enc = tuple(_gen_enc(v) for v in rect)
+            self._tr_ops.append((int(key), 1, 0) + enc + (None,))
+            self._tr_late[len(self._tr_ops) - 1] = [("fill", int(key)) + enc]
+            # every cell the edit can reach may have been written: get() there warns
+            g._maybe[min(c[0] for c in cases):max(c[2] for c in cases), min(c[1] for c in cases):max(c[3] for c in cases)] = True
+
+    def _place_region_sym(self, top, size):
+        """place_obj's sampling rectangle with a draw in `top` / `size`: constants clamped here, the rest on the device
+        (base.py:692-695); returns the operands and the hull of the rectangles the draws can produce"""
+        top = (0, 0) if top is None else tuple(top)
+        size = (self.width, self.height) if size is None else tuple(size)
+        x0, y0, x1, y1 = top[0], top[1], _gen_add(top[0], size[0]), _gen_add(top[1], size[1])
+        for v in (x0, y0, x1, y1):
+            if not isinstance(v, GenDraw):
+                GenDraw._int(v, "place_obj(top=, size=) of %s" % type(v).__name__)
+        x0, y0 = (v if isinstance(v, GenDraw) else max(int(v), 0) for v in (x0, y0))
+        x1, y1 = (v if isinstance(v, GenDraw) else min(int(v), lim) for v, lim in ((x1, self.width), (y1, self.height)))
+        clamped = [(max(a, 0), max(b, 0), min(c, self.width), min(d, self.height)) for a, b, c, d in self._tr_cases(x0, y0, x1, y1)]
+        if any(c <= a or d <= b for a, b, c, d in clamped):
+            raise ValueError("place_obj: the sampling rectangle [%r, %r) x [%r, %r) is empty for some value the draws can take"
+                             % (x0, x1, y0, y1))
+        hull = (min(c[0] for c in clamped), min(c[1] for c in clamped), max(c[2] for c in clamped), max(c[3] for c in clamped))
+        return (x0, y0, x1, y1), hull
+
     def _trace_gen_grid(self):
         self._tracing = True
         self._tr_grid = None
@@ -991,6 +1145,10 @@ class MultiGridEnv(object):
         g = self._tr_grid
         if g is None or self.grid is not g:
             raise RuntimeError("_gen_grid must assign self.grid = MultiGrid((width, height))")
+        kw = self.agent_spawn_kwargs or {}
+        if _any_draw(*[v for k in ("top", "size") if kw.get(k) is not None for v in kw[k]]):
+            raise NotImplementedError("agent_spawn_kwargs with a _rand_int draw: the spawn rectangle is also used by respawn and "
+                                      "late spawns, long after the reset that made the draw — not supported")
         if len(self._tr_ops) > N.MAX_GEN:
             fills = sum(1 for op in self._tr_ops if op[2] == 0)
             raise NotImplementedError("_gen_grid records %d reset-program ops — %d groups of random placements and %d rectangle "
@@ -1083,9 +1241,13 @@ class MultiGridEnv(object):
             raise NotImplementedError("inside _gen_grid agents are placed by reset() itself")
         max_tries = int(max(1, min(max_tries, 1e5)))
         key = self.obj_reg.get_key(obj)
-        region = self._place_region(top, size)
+        if _any_draw(*[v for r in (top, size) if r is not None for v in r]):
+            operands, region = self._place_region_sym(top, size)    # (region: the hull — every cell some draw can sample)
+            operands = tuple(_gen_enc(v) for v in operands)
+        else:
+            operands = region = self._place_region(top, size)
         rej = self._reject_table(reject_fn, region)
-        op = (key, 1, max_tries) + region + (None if rej is None else rej.tobytes(),)
+        op = (key, 1, max_tries) + operands + (None if rej is None else rej.tobytes(),)
         x0, y0, x1, y1 = region
         may = self._tr_grid._shadow[x0:x1, y0:y1] == 0          # (only empty cells accept a placement, base.py:672-679)
         if rej is not None:
@@ -1348,8 +1510,12 @@ class MultiGridEnv(object):
         host_ops = (N.GenOp * max(1, len(ops)))()
         for i, (obj, count, max_tries, x0, y0, x1, y1, rej) in enumerate(ops):
             # (the library cannot look into device memory from the host: what the kernels rely on is checked here)
-            assert (1 if max_tries > 0 else 0) <= obj < len(self.obj_reg.objs) and count >= 0 and max_tries >= 0
-            assert 0 <= x0 < x1 <= self.width and 0 <= y0 < y1 <= self.height
+            if max_tries < 0:       # a `_rand_int` draw: obj is its register
+                assert 0 <= obj < N.GEN_DRAWS
+            else:
+                assert (1 if max_tries > 0 else 0) <= obj < len(self.obj_reg.objs) and count >= 0
+                # (a rectangle with a draw operand was proved by the recorder and is clamped on the device)
+                assert any(v & N.GEN_SYM for v in (x0, y0, x1, y1)) or (0 <= x0 < x1 <= self.width and 0 <= y0 < y1 <= self.height)
             o = host_ops[i]
             o.obj, o.count, o.max_tries, o.x0, o.y0, o.x1, o.y1 = obj, count, max_tries, x0, y0, x1, y1
             o.reject = -1
@@ -1855,11 +2021,13 @@ class MultiGridEnv(object):
             out = list(p["sym"])
             late = p.get("late", {})
             for i, (k, c, t, x0, y0, x1, y1, rej) in enumerate(p["ops"]):
-                if t == 0:               # a static edit after a placement: its symbolic form, once
+                if t <= 0:               # a static edit after a placement, or a draw: its symbolic form, once
                     out.extend(late.get(i, []))
                     continue
                 full = (x0, y0, x1, y1) == (0, 0, self.width, self.height)
-                if rej is not None:      # reject_fn, tabulated: the rejected cells of the sampling rectangle
+                if any(v & N.GEN_SYM for v in (x0, y0, x1, y1)):      # (encoded operands: no oracle replays these)
+                    out.append(("place_sym", k, c, t, x0, y0, x1, y1))
+                elif rej is not None:      # reject_fn, tabulated: the rejected cells of the sampling rectangle
                     cells = np.argwhere(np.frombuffer(rej, np.uint8).reshape(self.width, self.height))
                     out.append(("place", k, c, t, x0, y0, x1, y1, tuple((int(x), int(y)) for x, y in cells)))
                 else:

@@ -457,6 +457,24 @@ MG_HD bool place_agent(const MgConfig& cfg, const uint8_t* oflags, uint8_t* g, M
     return false;
 }
 
+// an operand of a reset-program op: a plain integer, or `const +- draw[r]` (marlgrid_hip.h MG_GEN_SYM); branch-free
+MG_HD int gen_operand(int32_t v, uint64_t draws) {
+    const bool sym = (v & MG_GEN_SYM) != 0;
+    const int r = (v >> MG_GEN_DRAW_SHIFT) & (MG_GEN_DRAWS - 1);        // (32-bit halves: no 64-bit shift by a variable)
+    const uint32_t half = (r & 4) ? (uint32_t)(draws >> 32) : (uint32_t)draws;
+    const int d = sym ? (int)((half >> ((r & 3) * 8)) & 0xFFu) : 0;
+    const int c = sym ? (int)(int16_t)(v & 0xFFFF) : v;
+    return (v & MG_GEN_NEG) ? c - d : c + d;
+}
+// One register that the compiler keeps as ONE register: a value packed for the length of a loop is not taken apart ahead of
+// the loop again (reset_env's sampling rectangle: four registers per lane across every RNG refill otherwise)
+MG_HD uint32_t keep_packed(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
+
 // ---- reset (base.py:402-416) ----------------------------------------------------------------------
 // `_gen_grid` as a static template + ordered rejection-sampled placements (base.py:664-708;
 // envs/cluttered.py:25-36, envs/empty.py:9-16, envs/goalcycle.py:30-51), then agent.reset(
@@ -473,20 +491,44 @@ MG_HD int reset_env(const MgConfig& cfg, const MgState& st, const MgGenProgram& 
         for (int i = 0; i < cfg.cells_stride / 16; i++) dst[i] = src[i];
     }
     int err = 0;
-    // place_obj(obj, max_tries) for non-agent objects: only an empty cell accepts (try_place_obj,
-    // base.py:669-679; no agent is on the fresh grid yet)
+    // `_rand_int` draws of this reset (marlgrid_hip.h MG_GEN_*): draw r in byte r of one scalar — coordinates are uint8 —, read
+    // and written with shifts like step_begin's nibble permutation (an indexed private array would live in scratch memory)
+    uint64_t draws = 0;
     for (int o = 0; o < prog.n_ops && !err; o++) {
-        const MgGenOp op = prog.ops[o];
-        if (op.max_tries == 0) {      // a static edit after a placement (put_obj / wall helper): replaces what is there
+        MgGenOp op = prog.ops[o];
+        // operands `const +- draw[r]` (branch-free: a plain operand evaluates to itself); a fill or place rectangle with one is
+        // clamped to the grid — place_obj's own clamp, base.py:692-695; for a fill: whatever program a caller hands over,
+        // nothing is written outside the env's grid slice
+        const bool sym = ((op.x0 | op.y0 | op.x1 | op.y1) & MG_GEN_SYM) != 0 && op.max_tries >= 0;
+        op.x0 = gen_operand(op.x0, draws); op.y0 = gen_operand(op.y0, draws);
+        op.x1 = gen_operand(op.x1, draws); op.y1 = gen_operand(op.y1, draws);
+        const int lo = sym ? 0 : -MG_GEN_SYM, hx = sym ? cfg.W : MG_GEN_SYM, hy = sym ? H : MG_GEN_SYM;
+        op.x0 = op.x0 < lo ? lo : op.x0; op.y0 = op.y0 < lo ? lo : op.y0;
+        op.x1 = op.x1 > hx ? hx : op.x1; op.y1 = op.y1 > hy ? hy : op.y1;
+        if (sym && op.max_tries > 0 && (op.x1 <= op.x0 || op.y1 <= op.y0)) { err = MG_ERR_VALUE; break; }   // randint(low >= high)
+        if (op.max_tries < 0) {       // draw[obj] = _rand_int(x0, x1) = np_random.randint(x0, x1); a one-value range draws nothing
+            const int span = op.x1 - op.x0 - 1;
+            const uint32_t v = (uint32_t)(op.x0 + (int)mt.bounded((uint32_t)(span < 0 ? 0 : span))) & 0xFFu;
+            const int sh = (op.obj & (MG_GEN_DRAWS - 1)) * 8;
+            draws = (draws & ~(0xFFull << sh)) | ((uint64_t)v << sh);
+            continue;
+        }
+        if (op.max_tries == 0) {      // a static edit after a placement or a draw (put_obj / wall helper): replaces what is there
             for (int x = op.x0; x < op.x1; x++)
                 for (int y = op.y0; y < op.y1; y++) g[x * H + y] = (uint8_t)op.obj;
             continue;
         }
+        // place_obj(obj, max_tries) for non-agent objects: only an empty cell accepts (try_place_obj, base.py:669-679; no
+        // agent is on the fresh grid yet)
+        // (the rectangle is per env now: x0 | y0 << 8 | (x1 - x0 - 1) << 16 | (y1 - y0 - 1) << 24 — W, H <= 255 — in one register)
+        uint32_t rect = (uint32_t)op.x0 | (uint32_t)op.y0 << 8 | (uint32_t)(op.x1 - op.x0 - 1) << 16 | (uint32_t)(op.y1 - op.y0 - 1) << 24;
         for (int c = 0; c < op.count && !err; c++) {
             bool ok = false;
             for (int t = 0; t < op.max_tries; t++) {
-                const int x = op.x0 + (int)mt.bounded((uint32_t)(op.x1 - op.x0 - 1));
-                const int y = op.y0 + (int)mt.bounded((uint32_t)(op.y1 - op.y0 - 1));
+                rect = keep_packed(rect);
+                const int x = (int)(rect & 0xFFu) + (int)mt.bounded((rect >> 16) & 0xFFu);
+                rect = keep_packed(rect);
+                const int y = (int)((rect >> 8) & 0xFFu) + (int)mt.bounded(rect >> 24);
                 const int cell = x * H + y;
                 if (op.reject >= 0 && prog.reject[(size_t)op.reject * cfg.cells_stride + cell]) continue;   // reject_fn(pos)
                 if (g[cell] == 0) { g[cell] = (uint8_t)op.obj; ok = true; break; }

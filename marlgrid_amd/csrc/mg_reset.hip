@@ -22,8 +22,10 @@ __device__ __forceinline__ uint8_t* stage_oflags(const MgConfig& cfg, uint64_t* 
 }
 static size_t reset_lds(const MgConfig& cfg) { return reset_scratch_bytes(cfg.n_agents, kBlock); }
 
-__global__ __launch_bounds__(kBlock) void reset_kernel(MgConfig cfg, MgState st, MgGenProgram prog,
-                                                       const uint8_t* __restrict__ mask) {
+// (6 waves per SIMD, 80 VGPRs: the register allocator is held to the class the kernel had before a reset program could carry
+// per-env draws; it gets there without a spill since reset_env keeps the sampling rectangle in one register)
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(6))) void reset_kernel(
+    MgConfig cfg, MgState st, MgGenProgram prog, const uint8_t* __restrict__ mask) {
     extern __shared__ __attribute__((aligned(16))) uint64_t s_rec[];  // [n][kBlock]
     uint8_t* s_oflags = stage_oflags(cfg, s_rec);
     const int tid = threadIdx.x;

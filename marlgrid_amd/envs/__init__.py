@@ -1,19 +1,27 @@
 """Scenario classes and the ids the reference registers with gym (marlgrid/envs/__init__.py:20-121).
 
 gym is not a dependency: ids live in a module-level table and `make(id, batch_size=..., device=...)`
-stands in for `gym.make`.  `DoorKeyEnv` is absent on purpose — upstream's cannot be constructed
-(`self._rand_int` is undefined, doorkey.py:26,34).
+stands in for `gym.make`.
+
+`DoorKeyEnv` is upstream's envs/doorkey.py with gym-minigrid's `_rand_int` (upstream's own cannot be constructed: it never
+defines the method, doorkey.py:26,34).  Its `_gen_grid` lays the room out from random draws — `MultiGridEnv._rand_int`
+inside `_gen_grid` is recorded and drawn per env on the device at every reset.  A recorded `_gen_grid` may compute with a
+draw (`draw +- int`) and use it as a coordinate or extent of put_obj / grid.set / the wall helpers, in place_obj's `top` /
+`size` and as a bound of a later `_rand_int`; it still cannot BRANCH on one (compare it, index or loop with it), choose an
+object by it, put it into `agent_spawn_kwargs`, or have a `reject_fn` that depends on it.  Upstream registers no DoorKey
+id; the ids in `extension_envs` are this package's own and are built by `make` like the registered ones.
 """
 import functools
 import random
 
 from ..agents import GridAgentInterface
 from ..base import MultiGridEnv
-from .scenarios import ClutteredGoalCycleEnv, ClutteredMultiGrid, EmptyMultiGrid, VisibilityTestEnv
+from .scenarios import ClutteredGoalCycleEnv, ClutteredMultiGrid, DoorKeyEnv, EmptyMultiGrid, VisibilityTestEnv
 
 _PALETTE = ("red", "blue", "purple", "orange", "olive", "pink")     # per-slot agent colours of a registered id
 _registry = {}            # id -> factory(**constructor kwargs)
 registered_envs = []      # ids, in registration order (upstream's list of the same name)
+extension_envs = []       # ids upstream does not register (DoorKey): `make` builds them, `registered_envs` stays upstream's list
 
 
 def _construct(env_class, n_agents, geometry, agent_color, fixed, **extra):
@@ -25,13 +33,14 @@ def _construct(env_class, n_agents, geometry, agent_color, fixed, **extra):
 
 
 def register_marl_env(env_name, env_class, n_agents, grid_size, view_size, view_tile_size=8, view_offset=0,
-                      agent_color=None, env_kwargs={}):
-    """Same signature as upstream (:20-55).  `view_tile_size` is accepted and — as upstream — ignored."""
+                      agent_color=None, env_kwargs={}, listed_in=None):
+    """Same signature as upstream (:20-55).  `view_tile_size` is accepted and — as upstream — ignored.  `listed_in` (not
+    upstream's): the list of ids the new one joins, `registered_envs` unless given (`extension_envs` for this package's own)."""
     if n_agents > len(_PALETTE):
         raise AssertionError("a registered id has at most %d agents" % len(_PALETTE))
     _registry[env_name] = functools.partial(_construct, env_class, n_agents, (view_size, view_offset), agent_color,
                                             dict(env_kwargs, grid_size=grid_size))
-    registered_envs.append(env_name)
+    (registered_envs if listed_in is None else listed_in).append(env_name)
 
 
 def make(env_name, pipeline=None, devices=None, **kwargs):
@@ -51,7 +60,7 @@ def make(env_name, pipeline=None, devices=None, **kwargs):
     try:
         factory = _registry[env_name]
     except KeyError:
-        raise KeyError("unknown env id %r; registered: %s" % (env_name, ", ".join(registered_envs))) from None
+        raise KeyError("unknown env id %r; registered: %s" % (env_name, ", ".join(registered_envs + extension_envs))) from None
     if devices is not None:
         from ..sharding import DeviceShards, merge_share
         if pipeline is not None:
@@ -108,4 +117,6 @@ for _row in (
 ):
     register_marl_env(_row[0], _row[1], n_agents=_row[2], grid_size=_row[3], view_size=_row[4], view_offset=_row[5],
                       env_kwargs=_row[6])
+for _row in (("MarlGrid-2AgentDoorKey6x6-v0", 6), ("MarlGrid-2AgentDoorKey8x8-v0", 8)):
+    register_marl_env(_row[0], DoorKeyEnv, n_agents=2, grid_size=_row[1], view_size=7, listed_in=extension_envs)
 del _row

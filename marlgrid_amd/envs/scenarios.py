@@ -2,7 +2,7 @@
 
 Each class describes a layout through `_gen_grid`, written against the same `MultiGrid` /
 `put_obj` / `place_obj` vocabulary as upstream's `marlgrid/envs/{empty,cluttered,goalcycle,
-viz_test}.py`.  Here `_gen_grid` does not build a grid: it is *recorded* (static cells -> a template,
+viz_test,doorkey}.py`.  Here `_gen_grid` does not build a grid: it is *recorded* (static cells -> a template,
 `place_obj` calls -> an ordered rejection-sampling program) and the HIP reset kernel replays the
 recording for every env of the batch with that env's own RNG (see `MultiGridEnv._trace_gen_grid`).
 
@@ -12,7 +12,7 @@ the constructor-time grid differs from the grid of the first user `reset()` (clu
 goalcycle.py:13-40) — this consumes RNG draws and is part of seed-for-seed parity.
 """
 from ..base import MultiGrid, MultiGridEnv
-from ..objects import BonusTile, Goal, Wall
+from ..objects import BonusTile, Door, Goal, Key, Wall
 
 
 def _clutter_count(env, n_clutter, clutter_density):
@@ -116,4 +116,22 @@ class VisibilityTestEnv(_WalledRoom):
     def _gen_grid(self, width, height):
         self._room(width, height)
         self.grid.horz_wall(0, height // 2, width - 3, obj_type=Wall)
+        self._spawn_anywhere()
+
+
+class DoorKeyEnv(_WalledRoom):
+    """A room split by a wall at a random column, a locked door at a random row of it, the key somewhere on the left and
+    the goal in the bottom-right corner (upstream's envs/doorkey.py:15-41, with gym-minigrid's `_rand_int`).  The split
+    column and the door row are `_rand_int` draws: every env lays out its own room at every reset, on the device.  As
+    upstream the door row is drawn from `1 .. width - 3`, so the grid must be at least that high."""
+    mission = "use the key to open the door and then get to the goal"
+
+    def _gen_grid(self, width, height):
+        self._room(width, height)
+        self._corner_goal(width, height)
+        split = self._rand_int(2, width - 2)                 # the splitting wall
+        self.grid.vert_wall(split, 0)
+        door = self._rand_int(1, width - 2)                  # (upstream draws the row from the WIDTH)
+        self.put_obj(Door(color="yellow", state=Door.states.locked), split, door)
+        self.place_obj(obj=Key("yellow"), top=(0, 0), size=(split, height))
         self._spawn_anywhere()

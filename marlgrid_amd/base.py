@@ -1120,13 +1120,16 @@ class MultiGridEnv(object):
         (base.py:692-695); returns the operands and the hull of the rectangles the draws can produce"""
         top = (0, 0) if top is None else tuple(top)
         size = (self.width, self.height) if size is None else tuple(size)
-        x0, y0, x1, y1 = top[0], top[1], _gen_add(top[0], size[0]), _gen_add(top[1], size[1])
-        for v in (x0, y0, x1, y1):
+        for v in tuple(top) + tuple(size):
             if not isinstance(v, GenDraw):
                 GenDraw._int(v, "place_obj(top=, size=) of %s" % type(v).__name__)
-        x0, y0 = (v if isinstance(v, GenDraw) else max(int(v), 0) for v in (x0, y0))
+        # upstream clamps `top` first and adds `size` to the CLAMPED top (base.py:692, 695): a rectangle that starts outside the
+        # grid keeps its extent.  A constant top is clamped here; a drawn one on the device, which moves the far edge with it
+        x0, y0 = (v if isinstance(v, GenDraw) else max(int(v), 0) for v in top)
+        x1, y1 = _gen_add(x0, size[0]), _gen_add(y0, size[1])
         x1, y1 = (v if isinstance(v, GenDraw) else min(int(v), lim) for v, lim in ((x1, self.width), (y1, self.height)))
-        clamped = [(max(a, 0), max(b, 0), min(c, self.width), min(d, self.height)) for a, b, c, d in self._tr_cases(x0, y0, x1, y1)]
+        clamped = [(max(a, 0), max(b, 0), min(max(a, 0) + (c - a), self.width), min(max(b, 0) + (d - b), self.height))
+                   for a, b, c, d in self._tr_cases(x0, y0, x1, y1)]
         if any(c <= a or d <= b for a, b, c, d in clamped):
             raise ValueError("place_obj: the sampling rectangle [%r, %r) x [%r, %r) is empty for some value the draws can take"
                              % (x0, x1, y0, y1))

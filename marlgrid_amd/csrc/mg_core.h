@@ -502,6 +502,10 @@ MG_HD int reset_env(const MgConfig& cfg, const MgState& st, const MgGenProgram& 
         const bool sym = ((op.x0 | op.y0 | op.x1 | op.y1) & MG_GEN_SYM) != 0 && op.max_tries >= 0;
         op.x0 = gen_operand(op.x0, draws); op.y0 = gen_operand(op.y0, draws);
         op.x1 = gen_operand(op.x1, draws); op.y1 = gen_operand(op.y1, draws);
+        // (place_obj clamps `top` FIRST and adds `size` to the clamped top: a rectangle that starts left of / above the grid
+        // keeps its extent and moves in — bottom = max(top, 0) + size, not top + size)
+        const bool plc = sym && op.max_tries > 0;
+        op.x1 -= (plc && op.x0 < 0) ? op.x0 : 0; op.y1 -= (plc && op.y0 < 0) ? op.y0 : 0;
         const int lo = sym ? 0 : -MG_GEN_SYM, hx = sym ? cfg.W : MG_GEN_SYM, hy = sym ? H : MG_GEN_SYM;
         op.x0 = op.x0 < lo ? lo : op.x0; op.y0 = op.y0 < lo ? lo : op.y0;
         op.x1 = op.x1 > hx ? hx : op.x1; op.y1 = op.y1 > hy ? hy : op.y1;

@@ -111,6 +111,8 @@ struct MgoEnv {
     int32_t abonus[MGO_MAX_AGENTS];                    /* agent.bonus_state, -1 = None */
     double aprestige[MGO_MAX_AGENTS];                  /* agent.prestige (agents.py:141-153,168) */
     int32_t step_count;
+    int draw[MGO_MAX_DRAWS];                           /* the `_rand_int` values of the running / last `_gen_grid` */
+    int draw_words[MGO_MAX_DRAWS];                     /* RNG words each consumed; -1: not drawn */
     uint32_t mt[MT_N];
     int32_t mt_pos;
 };
@@ -399,11 +401,18 @@ int32_t mgo_put_obj(MgoEnv* e, int32_t obj, int32_t x, int32_t y) {
     return MGO_OK;
 }
 
+/* a coordinate computed from a `_rand_int` value: plain int arithmetic on the Python variable */
+static int operand(const MgoEnv* e, const MgoOperand* o) {
+    return o->reg < 0 ? o->c : o->c + o->sign * e->draw[o->reg];
+}
+
 /* `_gen_grid`: envs/empty.py:9-16, envs/cluttered.py:25-36, envs/goalcycle.py:30-51,
- * envs/viz_test.py:9-15; wall helpers base.py:160-176 */
+ * envs/viz_test.py:9-15, envs/doorkey.py:15-41 (`_rand_int`: gym-minigrid's np_random.randint(low, high)), the scenarios of
+ * tests/draw_envs.py; wall helpers base.py:160-176 */
 static int gen_grid(MgoEnv* e, int which) {
     const MgoConfig* cfg = &e->sh->cfg;
     int nc = cfg->W * cfg->H;
+    for (int r = 0; r < MGO_MAX_DRAWS; r++) { e->draw[r] = 0; e->draw_words[r] = -1; }
     memset(e->cell, 0, nc * sizeof(int32_t));          /* MultiGrid((W,H)) — base.py:87-101 */
     memset(e->cell_nagents, 0, nc * sizeof(int32_t));
     for (int g = 0; g < cfg->n_gen[which]; g++) {
@@ -429,6 +438,40 @@ static int gen_grid(MgoEnv* e, int which) {
                 if (rc != MGO_OK) return rc;
             }
             break;
+        case MGO_GEN_DRAW: {
+            /* v = self._rand_int(lo, hi) -> np_random.randint(lo, hi): lo + bounded(hi - lo - 1); ValueError on low >= high */
+            int lo = operand(e, &op->a[0]), hi = operand(e, &op->a[1]);
+            if (hi <= lo || op->obj < 0 || op->obj >= MGO_MAX_DRAWS) return MGO_ERR_VALUE;
+            int before = e->mt_pos;
+            e->draw[op->obj] = lo + (int)mgo_bounded(e->mt, &e->mt_pos, (uint32_t)(hi - lo - 1));
+            e->draw_words[op->obj] = ((e->mt_pos - before) % MT_N + MT_N) % MT_N;
+            break;
+        }
+        case MGO_GEN_FILL: {
+            /* grid.set(x, y, obj) cell by cell (put_obj base.py:655-662, vert_wall / horz_wall / wall_rect base.py:160-176):
+             * `assert i >= 0 and i < self.width` (base.py:149-152) — nothing is clamped */
+            int x0 = operand(e, &op->a[0]), y0 = operand(e, &op->a[1]), x1 = operand(e, &op->a[2]), y1 = operand(e, &op->a[3]);
+            for (int x = x0; x < x1; x++)
+                for (int y = y0; y < y1; y++) {
+                    int rc = mgo_put_obj(e, op->obj, x, y);
+                    if (rc != MGO_OK) return rc;
+                }
+            break;
+        }
+        case MGO_GEN_PLACE_SYM: {
+            /* place_obj(obj, top=, size=) — base.py:692-695: top = max(top, 0); bottom = min(top + size, (W, H)) with the
+             * CLAMPED top; then np_random.randint(top, bottom) per try (ValueError on an empty range) */
+            int tx = operand(e, &op->a[0]), ty = operand(e, &op->a[1]);
+            int sx = operand(e, &op->a[2]) - tx, sy = operand(e, &op->a[3]) - ty;
+            int x0 = tx > 0 ? tx : 0, y0 = ty > 0 ? ty : 0;
+            int x1 = x0 + sx < cfg->W ? x0 + sx : cfg->W, y1 = y0 + sy < cfg->H ? y0 + sy : cfg->H;
+            if (x1 <= x0 || y1 <= y0) return MGO_ERR_VALUE;
+            for (int n = 0; n < op->count; n++) {
+                int rc = place_obj_in(e, op->obj, (double)op->max_tries, x0, y0, x1, y1, op->reject, 0, 0);
+                if (rc != MGO_OK) return rc;
+            }
+            break;
+        }
         }
     }
     return MGO_OK;
@@ -909,6 +952,10 @@ void mgo_rich_obs(const MgoEnv* e, int32_t k, double* reward, double* position2,
 void mgo_get_mt(const MgoEnv* e, uint32_t* mt624, int32_t* pos) {
     memcpy(mt624, e->mt, sizeof(e->mt));
     *pos = e->mt_pos;
+}
+
+void mgo_get_draws(const MgoEnv* e, int32_t* draws, int32_t* words) {
+    for (int r = 0; r < MGO_MAX_DRAWS; r++) { draws[r] = e->draw_words[r] < 0 ? -1 : e->draw[r]; words[r] = e->draw_words[r]; }
 }
 
 void mgo_set_agent_dir(MgoEnv* e, int32_t k, int32_t dir) { e->adir[k] = ((dir % 4) + 4) % 4; }

@@ -66,14 +66,30 @@ typedef struct {
     MgoFillOp fill[MGO_MAX_FILL];                     /* obj.render(img)                        */
 } MgoObjDesc;
 
-/* `_gen_grid` program (envs/empty.py, envs/cluttered.py, envs/goalcycle.py, envs/viz_test.py) */
+/* `_gen_grid` program (envs/empty.py, envs/cluttered.py, envs/goalcycle.py, envs/viz_test.py, envs/doorkey.py, and the
+ * test scenarios of tests/draw_envs.py whose layout depends on `self._rand_int(lo, hi)`).
+ *
+ * A `_gen_grid` that calls `_rand_int` keeps what it drew in Python variables and computes coordinates from them.  Here the
+ * values drawn in one `_gen_grid` run are a plain `int draw[]` of the env, and a coordinate that depends on one is an
+ * MgoOperand: `c`, or `c + sign * draw[reg]`, evaluated in plain int where it is used.
+ *   DRAW       draw[obj] = np_random.randint(a[0], a[1]) = a[0] + bounded(a[1] - a[0] - 1) (gym-minigrid's `_rand_int`); a
+ *              one-value range consumes no word; a[1] <= a[0]: ValueError
+ *   FILL       grid.set(x, y, obj or None) for every cell of [a[0], a[2]) x [a[1], a[3]) (put_obj / the wall helpers with
+ *              drawn coordinates).  NOT clamped: a cell outside the grid is grid.set's AssertionError (base.py:149-152)
+ *   PLACE_SYM  place_obj(obj, top=(a[0], a[1]), size=(a[2] - a[0], a[3] - a[1]), max_tries), `count` times, the rectangle
+ *              clamped as base.py:692-695 does: top first, then bottom = min(clamped top + size, (W, H)) */
 enum { MGO_GEN_WALL_RECT = 0, MGO_GEN_HORZ_WALL = 1, MGO_GEN_VERT_WALL = 2, MGO_GEN_PUT = 3,
-       MGO_GEN_PLACE = 4 };
+       MGO_GEN_PLACE = 4, MGO_GEN_DRAW = 5, MGO_GEN_FILL = 6, MGO_GEN_PLACE_SYM = 7 };
+#define MGO_MAX_DRAWS 16
+typedef struct {
+    int32_t c, reg, sign;    /* reg < 0: the constant c; else c + sign * draw[reg], sign +1 / -1 */
+} MgoOperand;
 typedef struct {
     int32_t kind, obj, count, x, y, w, h, max_tries;
     const uint8_t* reject;   /* place_obj(reject_fn=): the callback tabulated over the grid, index x*H + y, != 0 =
                               * rejected (base.py:700-701: a rejected draw is a spent try); NULL: none.  The
                               * caller keeps it alive. */
+    MgoOperand a[4];         /* DRAW: lo, hi (obj: the register); FILL / PLACE_SYM: x0, y0, x1, y1.  Unused by kinds 0-4 */
 } MgoGenOp;
 
 typedef struct {
@@ -133,6 +149,9 @@ void mgo_occlude(int32_t vs, int32_t ax, int32_t ay, const uint8_t* transp, uint
 void mgo_get_state(const MgoEnv* e, uint8_t* base, int32_t* agents7, int32_t* step_count);
 void mgo_get_prestige(const MgoEnv* e, double* out);
 void mgo_get_mt(const MgoEnv* e, uint32_t* mt624, int32_t* pos);
+/* the `_rand_int` values of the env's last `_gen_grid` run and the RNG words each of them consumed (MGO_MAX_DRAWS entries
+ * each; -1: that register was not drawn) */
+void mgo_get_draws(const MgoEnv* e, int32_t* draws, int32_t* words);
 void mgo_set_agent_dir(MgoEnv* e, int32_t k, int32_t dir);
 void mgo_set_carrying(MgoEnv* e, int32_t k, int32_t obj);
 /* test helper: overwrite a cell with a non-agent object id (env.put_obj, base.py:655-662) */

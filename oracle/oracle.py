@@ -23,7 +23,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmgoracle.so")
 
-MAX_AGENTS, MAX_OBJ, MAX_FILL, MAX_GEN = 32, 256, 8, 192
+MAX_AGENTS, MAX_OBJ, MAX_FILL, MAX_GEN, MAX_DRAWS = 32, 256, 8, 192, 16
 
 # objects.py:11-29
 COLORS = {
@@ -67,8 +67,13 @@ class ObjDesc(C.Structure):
                 ("is_key", C.c_int32), ("n_fill", C.c_int32), ("fill", FillOp * MAX_FILL)]
 
 
+class Operand(C.Structure):
+    _fields_ = [("c", C.c_int32), ("reg", C.c_int32), ("sign", C.c_int32)]
+
+
 class GenOp(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("kind", "obj", "count", "x", "y", "w", "h", "max_tries")] + [("reject", C.c_void_p)]
+    _fields_ = ([(n, C.c_int32) for n in ("kind", "obj", "count", "x", "y", "w", "h", "max_tries")] + [("reject", C.c_void_p)]
+                + [("a", Operand * 4)])
 
 
 class Config(C.Structure):
@@ -126,6 +131,8 @@ def lib():
         L.mgo_occlude.argtypes = [C.c_int32, C.c_int32, C.c_int32, u8p, u8p]
         L.mgo_get_state.argtypes = [vp, u8p, i32p, i32p]
         L.mgo_get_mt.argtypes = [vp, u32p, i32p]
+        L.mgo_get_draws.restype = None
+        L.mgo_get_draws.argtypes = [vp, i32p, i32p]
         L.mgo_get_prestige.argtypes = [vp, f64p]
         L.mgo_rich_obs.restype = None
         L.mgo_rich_obs.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), f64p, C.POINTER(C.c_int32)]
@@ -222,7 +229,19 @@ def _sprite(o):
     return []                                           # Floor / Lava / EmptySpace: unrenderable upstream
 
 
-_GEN_KIND = {"wall_rect": 0, "horz_wall": 1, "vert_wall": 2, "put": 3, "place": 4}
+_GEN_KIND = {"wall_rect": 0, "horz_wall": 1, "vert_wall": 2, "put": 3, "place": 4, "draw": 5, "fill": 6, "place_sym": 7}
+
+
+def _operands(op, vals):
+    """a coordinate of a gen op that may depend on a `_rand_int` value: an int, or ("d", reg, sign, const) for
+    `const + sign * draw[reg]`"""
+    for i, v in enumerate(vals):
+        if isinstance(v, tuple):
+            tag, reg, sign, const = v
+            assert tag == "d" and 0 <= reg < MAX_DRAWS and sign in (1, -1), v
+            op.a[i].c, op.a[i].reg, op.a[i].sign = int(const), int(reg), int(sign)
+        else:
+            op.a[i].c, op.a[i].reg, op.a[i].sign = int(v), -1, 1
 
 
 def reject_mask(cells, W, H):
@@ -338,6 +357,16 @@ def make_config(spec):
                     m = reject_mask(g[8], cfg.W, cfg.H)
                     cfg._keep.append(m)
                     op.reject = m.ctypes.data
+            elif g[0] == "draw":                     # ("draw", r, lo, hi): draw[r] = self._rand_int(lo, hi)
+                op.obj = g[1]
+                assert 0 <= g[1] < MAX_DRAWS
+                _operands(op, g[2:4])
+            elif g[0] == "fill":                     # ("fill", obj, x0, y0, x1, y1): grid.set over [x0, x1) x [y0, y1)
+                op.obj = g[1]
+                _operands(op, g[2:6])
+            elif g[0] == "place_sym":                # ("place_sym", obj, count, max_tries, x0, y0, x1, y1): top, top + size
+                op.obj, op.count, op.max_tries = g[1:4]
+                _operands(op, g[4:8])
     return cfg
 
 
@@ -440,6 +469,12 @@ class OracleEnv(object):
         pos = C.c_int32(0)
         self.L.mgo_get_mt(self.h, _p(mt, C.c_uint32), C.byref(pos))
         return mt, pos.value
+
+    def draws(self):
+        """the `_rand_int` values of the last `_gen_grid` run and the RNG words each consumed (-1: register not drawn)"""
+        d, w = np.zeros(MAX_DRAWS, np.int32), np.zeros(MAX_DRAWS, np.int32)
+        self.L.mgo_get_draws(self.h, _p(d, C.c_int32), _p(w, C.c_int32))
+        return d, w
 
     def set_dir(self, k, d):
         self.L.mgo_set_agent_dir(self.h, k, d)

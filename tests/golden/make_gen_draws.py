@@ -15,7 +15,8 @@ obs_full / obs_reset_full (one env) — plus
   venc_steps [K], venc_ctor_a<k> / venc_reset_a<k> [S][V][V][3], venc_step_a<k> [S][K][V][V][3]
         gen_obs_grid(agent k) + encode(vis_mask), as make_view_encodings.py records them (DoorKey: its pixels cannot be pinned)
 and asserts the conditions the fixtures exist for (every split column, gap rows, one-value ranges, rewards, pickups, an
-unlocked door).
+unlocked door; the eight-draw scenario: every register with more than one value, the overhanging place_obj clamped in some
+layouts and not in others).
 """
 import os
 import sys
@@ -81,7 +82,7 @@ def gen(name, out):
         v_ctor[:, si] = views(env)
         if pixels:
             crc_ctor[si] = [refstate.crc(x) for x in env.gen_obs()]
-        if kind == "doorkey":               # every _rand_int from here on: (low, high, value, the RNG moved)
+        if kind in ("doorkey", "eight"):    # every _rand_int from here on: (low, high, value, the RNG moved)
             def spied(low, high, _env=env, _draw=type(env)._rand_int):
                 before = rng_of(_env)
                 v = _draw(_env, low, high)
@@ -162,6 +163,14 @@ def gen(name, out):
             assert (np.isin(L[:, 2, :], (WALL, DOOR))).all() and (np.nonzero(L == DOOR)[1] == 2).all()
         stats.update(door_cells=len(doors), one_value_draws=len(one))
         assert (L == DOOR).reshape(len(L), -1).sum(axis=1).tolist() == [1] * len(L)
+    if kind == "eight":                     # eight draws a reset, in register order (draw_envs.py:eight)
+        per = np.array([d[2] for d in draws]).reshape(-1, 8)
+        assert all(len(set(per[:, r])) >= 2 for r in range(8)), "a register with one value"
+        assert (per[:, 6] < 3).any() and (per[:, 6] >= 3).any()         # the overhanging place_obj: clamped / not clamped
+        assert (per[:, 4] == per[:, 2]).all() and not any(d[3] for d in draws[4::8])      # _rand_int(c, c + 1): c, no RNG word
+        assert (per[:, 2] < per[:, 0]).all() and (per[:, 3] > per[:, 0]).all()            # bounded above / below by a draw
+        assert stats["goal_rewards"] >= 1
+        stats.update(layouts=len(per), overhang_clamped=int((per[:, 6] < 3).sum()))
     np.savez_compressed(out, **d)
     return stats
 

@@ -199,6 +199,25 @@ def test_split_program_operands_and_bookkeeping():
         env._tracing = False
 
 
+def test_place_obj_clamps_the_top_first_and_adds_the_size_to_the_clamped_top():
+    """base.py:692-695: `top = max(top, 0)`, THEN `bottom = min(top + size, (W, H))`.  A drawn top is clamped on the device,
+    which moves the far edge with it (the program keeps top and top + size); a constant one here, size added afterwards"""
+    def gen(self, w, h):
+        _room(self, w, h)
+        d = self._rand_int(0, 6)
+        self.place_obj(Wall(), top=(d - 3, 0), size=(4, h + 5), max_tries=100)
+        self.place_obj(Goal(color="green", reward=1), top=(-2, -1), size=(d + 1, 3), max_tries=100)
+    _, (_, ops) = _record(gen)
+    assert ops[1:] == [(1, 1, 100, D_(0, -3), 0, D_(0, 1), 9, None),
+                       (2, 1, 100, 0, 0, D_(0, 1), 3, None)]          # upstream: [0, 0 + d + 1) x [0, 0 + 3), not d - 1 and 2
+
+    def empty(self, w, h):                                           # [w + d - 3, ...): past the right edge for d = 3
+        _room(self, w, h)
+        self.place_obj(Wall(), top=(self._rand_int(0, 4) + w - 3, 0), size=(4, h))
+    with pytest.raises(ValueError):
+        _record(empty)
+
+
 def test_static_edits_after_a_draw_go_into_the_program_unmerged():
     def gen(self, w, h):
         _room(self, w, h)

@@ -2,8 +2,10 @@
 resets — mg_reset, the step kernel, the encoded-views kernel and the fused render kernels — against the reference's own
 trajectories (tests/golden/gendraws_*.npz) and against the same `reset_env` text run on the host (tests/native).
 
-NOT covered here: the grid-in-place render kernel (grids beyond LDS) with a draw program — it shares `reset_env`, but a
-reference golden of a 150 x 150 grid is too slow to make."""
+The grid-in-place render kernel (grids beyond LDS) with a draw program is not covered HERE — a reference golden of a
+160 x 150 grid is too slow to make — but in tests/test_hip_gen_draws_oracle.py (D6), against the oracle, which
+tests/test_oracle_gen_draws.py pins to the live reference on that grid; the same file holds the wide differentials of every
+scenario of this one (4 099 envs, every env compared)."""
 import os
 import sys
 

@@ -297,14 +297,19 @@ class _EpisodeRef(object):
 
 # ---- the driver ---------------------------------------------------------------------------------------------------------
 def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mode="same_step", episode_info=False,
-        obs_format="image", stagger=False, after_step=None):
-    """Step `subject` and the oracle of scenarios.registered(name) for T steps (actions RandomState(action_seed).randint(0, 7)).
+        obs_format="image", stagger=False, after_step=None, spec=None, watch=None):
+    """Step `subject` and the oracle of `spec` (default: scenarios.registered(name)) for T steps (actions
+    RandomState(action_seed).randint(0, 7)).
+    watch(t, envs, mask): called with the ORACLE's envs after every reset on its side — t = 0: reset() (mask: everyone);
+    after step t: the envs whose reset ran in that call (same-step mode: those that ended in it; next-step mode: those that had
+    ended in the call before); after a staggered reset by hand.  What a test requires of its own coverage it reads there.
     mode: the subject's auto-reset mode; stagger: during the first 100 steps env b is reset by hand after step b % 100 (0-based),
     subject and oracle; after_step(t, subject): called between two steps (fault injection in the driver's own tests).
     -> dict(episodes (B,), draws (B,) RNG words drawn per env, blocks = draws / 624, partial_done_steps: steps on which some
     but not all envs ended, terminal_obs (B,): terminal observations compared per env, seconds: where the time went)"""
     B, n = subject.B, subject.n
-    spec = scenarios.registered(name)
+    if spec is None:
+        spec = scenarios.registered(name)
     use_ep = episode_info or mode == "next_step"
     ref = _EpisodeRef(spec, seeds, mode) if use_ep else _SameStepRef(spec, seeds)
     envs = ref.envs
@@ -400,6 +405,9 @@ def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mo
     obs = subject.reset()
     ref.reset()
     last_pos = subject.mt_pos().astype(np.int64)
+    if watch is not None:
+        watch(0, envs, np.ones(B, bool))
+    prev_done = np.zeros(B, bool)
     if subject.has_obs:
         check_obs(0, obs, None, what="observations of reset()")
     rng = np.random.RandomState(action_seed)
@@ -412,6 +420,9 @@ def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mo
         lap("subject")
         pixels, r2, d2, want_info = ref.step(a, look and subject.has_obs and kind == "obs")
         lap("oracle")
+        if watch is not None:
+            watch(t, envs, prev_done if mode == "next_step" else d2)
+            prev_done = d2.copy()
         last_pos = count_draws(last_pos)
         bad = np.asarray(d, bool) != d2
         if bad.any():
@@ -457,6 +468,9 @@ def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mo
             mask = (np.arange(B) % 100) == t - 1
             obs = subject.reset(mask)
             ref.reset_envs(mask)
+            if watch is not None:
+                watch(t, envs, mask)
+                prev_done &= ~mask
             last_pos = count_draws(last_pos)
             if subject.has_obs and mask.any():
                 check_obs(t, obs, None, ids=np.nonzero(mask)[0], what="observations of reset(env_mask)")

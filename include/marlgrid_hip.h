@@ -25,6 +25,8 @@
  *   mg_step_ep / mg_step_render_ep / mg_step_encode_views_ep   the three steps above with an MgEpisode: next-step auto-reset
  *                   (the terminal state is returned, the env's next call is its reset) and the episode's flags, length and
  *                   return from the step's own launch (base.py:512, 576-581, 627-649)
+ *   mg_step_render_delta / mg_step_render_delta_ex   mg_step_render (_ex: with the encode and / or an MgEpisode) that does not
+ *                   store again the observation bands its output buffer already holds
  *   mg_put_obj      MultiGridEnv.put_obj (base.py:655-662)
  *   mg_place        MultiGridEnv.place_obj / try_place_obj outside _gen_grid (base.py:664-708)
  *   mg_render_frame MultiGridEnv.render's whole-grid image: MultiGrid.render(top_agent=None) +
@@ -363,6 +365,19 @@ int32_t mg_step_render_ep(const MgConfig* cfg, const MgState* st, const void* ac
 int32_t mg_step_encode_views_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes,
                                 float* rewards, const MgGenProgram* auto_reset, uint8_t* views, const MgEpisode* ep,
                                 void* stream);
+/* mg_step_render_delta that also writes what mg_step_render_encode (encode_out), mg_step_render_ep (ep) or BOTH would — the one
+ * launch with the encode and the episode outputs together; it has no non-delta twin.  obs, signature, flags: as for
+ * mg_step_render_delta (the same signature serves both calls: a buffer may be written by either); encode_out, ep: as for the
+ * two calls named, either may be NULL.  The bytes in `obs`, in `encode_out` and in the episode outputs after the call are
+ * those of mg_step_render_ep (mg_step_render without ep) followed by mg_encode.
+ * MG_E_ARG (no device access): encode_out and ep both NULL (that call is mg_step_render_delta), a NULL or misaligned signature,
+ * an unknown flag, an MgEpisode mg_step_ep would refuse.
+ * MG_E_UNSUPPORTED — nothing launched, call mg_step_render_ep / mg_step_render_encode / mg_encode — unless mg_step_render_delta
+ * has the shape (view 7 with 8-pixel tiles, at most 3 agents, no 'prestige' agent, grid and atlas in LDS) and, with encode_out,
+ * mg_step_render_encode has it too (n_obj + 4 n_agents <= 256, the table fits LDS beside four waves). */
+int32_t mg_step_render_delta_ex(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes,
+                                float* rewards, const MgGenProgram* auto_reset, uint8_t* obs, uint16_t* signature,
+                                uint32_t flags, uint8_t* encode_out, const MgEpisode* ep, void* stream);
 
 /* ---- the observation kernel specialised on demand (mg_rtc.hip) -------------------------------------------------------
  *

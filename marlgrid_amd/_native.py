@@ -134,7 +134,7 @@ SYMBOLS = ["mg_abi_version", "mg_struct_sizes", "mg_host_flag_alloc", "mg_host_f
            "mg_encode", "mg_put_obj", "mg_place", "mg_render_frame", "mg_time_render_obs",
            "mg_render_obs_lds_bytes", "mg_render_kernel_name", "mg_step_encode_views", "mg_encode_views",
            "mg_episode_struct_size", "mg_step_ep", "mg_step_render_ep", "mg_step_encode_views_ep",
-           "mg_step_render_delta",
+           "mg_step_render_delta", "mg_step_render_delta_ex",
            "mg_spec_info_struct_size", "mg_render_specialize", "mg_step_render_spec", "mg_render_obs_spec",
            "mg_render_spec_release", "mg_rtc_source"]
 
@@ -207,6 +207,9 @@ def lib():
     L.mg_step_render_encode.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp, vp]
     # (cfg, st, actions, action_bytes, rewards, auto_reset, obs, signature, flags, stream)
     L.mg_step_render_delta.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp, C.c_uint32, vp]
+    # (cfg, st, actions, action_bytes, rewards, auto_reset, obs, signature, flags, encode_out, ep, stream)
+    L.mg_step_render_delta_ex.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp, C.c_uint32,
+                                          vp, C.POINTER(Episode), vp]
     L.mg_step_encode_views.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp]
     L.mg_encode_views.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp]
     L.mg_episode_struct_size.argtypes = []

@@ -565,7 +565,9 @@ class MultiGridEnv(object):
         # The returned tensors are VIEWS of buffers the env owns: a caller that writes into them calls invalidate_obs() (or
         # constructs with obs_delta=False).  "auto": where the step is the one fused image launch without episode outputs or
         # encode_in_step and the library has an instantiation for the shape (view 7, 8-pixel tiles, <= 3 agents, none
-        # 'prestige'); True: the same, but a configuration that cannot is an error; False: every step stores every byte.
+        # 'prestige'); True: the same, but a configuration that cannot is an error — and ALSO with episode_info,
+        # auto_reset="next_step", encode_in_step or any mix of them (mg_step_render_delta_ex: the episode outputs, the grid
+        # encoding or both from the one delta launch; "auto" leaves those steps as they are); False: every step stores every byte.
         if obs_delta not in ("auto", True, False):
             raise ValueError("obs_delta must be 'auto', True or False (got %r)" % (obs_delta,))
         self.obs_delta = obs_delta
@@ -1642,7 +1644,14 @@ class MultiGridEnv(object):
         fused = self.fused_step and not self._hetero
         encoding_written = False
         rc = None       # the fused call's answer.  (MG_E_UNSUPPORTED: nothing was launched, this configuration has no such instantiation)
-        if fused and self._encoded:
+        if self.obs_delta is True and (ep is not None or self.encode_in_step):
+            # obs_delta=True with episode outputs and / or encode_in_step: the delta launch that writes them too — with both, the
+            # one launch that has no non-delta twin (the table's path, like the plain delta: its one shape is on the table).
+            # A demand: an env whose step is not the fused image launch (view groups, fused_step=False, encoded views) raises
+            # here instead of stepping without it.
+            rc = self._launch_step_delta_ex(head, ep, stream)
+            encoding_written = self.encode_in_step
+        elif fused and self._encoded:
             # the step and every agent's encoded view, one call
             rc = (L.mg_step_encode_views if ep is None else L.mg_step_encode_views_ep)(*head, self.obs.data_ptr(), *tail)
         elif fused and ep is not None:
@@ -1687,8 +1696,10 @@ class MultiGridEnv(object):
 
     def _delta_wanted(self):
         """obs_delta: is this env's step the launch that has a delta twin (and has the library not said no yet)"""
-        return (self._delta_ok and not self._encoded and self.fused_step and not self._hetero and not self._use_ep
-                and not self.encode_in_step)
+        if not (self._delta_ok and not self._encoded and self.fused_step and not self._hetero):
+            return False
+        # ("auto": the plain step alone; with episode outputs or encode_in_step only when asked for — obs_delta=True)
+        return self.obs_delta is True or not (self._use_ep or self.encode_in_step)
 
     def _launch_step_delta(self, head, stream):
         """mg_step_render_delta into the current buffer set.  Whether a band is stored is decided on the device alone, against
@@ -1697,8 +1708,8 @@ class MultiGridEnv(object):
         r = self._ring[self._ring_i]
         if not self._delta_wanted() or r["sig"] is None:
             if self.obs_delta is True:
-                raise NotImplementedError("obs_delta=True needs the fused image step without episode outputs, encode_in_step or "
-                                          "view groups, and a shape the library has a delta instantiation for")
+                raise NotImplementedError("obs_delta=True needs the fused image step without view groups, and a shape the library "
+                                          "has a delta instantiation for (view 7 at 8-pixel tiles, at most 3 agents, no 'prestige' agent)")
             return None
         rc = self._lib.mg_step_render_delta(*head, self.obs.data_ptr(), r["sig"].data_ptr(), 0, stream)
         if rc == N.E_UNSUPPORTED:
@@ -1708,6 +1719,26 @@ class MultiGridEnv(object):
             return self._launch_step_delta(head, stream)
         self._delta_launches += 1
         return rc
+
+    def _launch_step_delta_ex(self, head, ep, stream):
+        """mg_step_render_delta_ex into the current buffer set (obs_delta=True with episode outputs and / or encode_in_step): the
+        same signatures, the same invalidation points as _launch_step_delta.  obs_delta=True is a demand: a configuration the
+        library has no such instantiation for raises."""
+        r = self._ring[self._ring_i]
+        what = " + ".join(w for w, on in (("episode outputs", ep is not None), ("encode_in_step", self.encode_in_step)) if on)
+        if self._delta_wanted() and r["sig"] is not None:
+            enc = self._encoding_buffer().data_ptr() if self.encode_in_step else None
+            rc = self._lib.mg_step_render_delta_ex(*head, self.obs.data_ptr(), r["sig"].data_ptr(), 0, enc, ep, stream)
+            if rc != N.E_UNSUPPORTED:
+                self._delta_launches += 1
+                return rc
+            self._delta_ok = False      # (nothing was launched)
+            for q in self._ring:
+                q["sig"] = None
+        raise NotImplementedError("obs_delta=True with %s: no delta launch for this configuration — it needs the fused image step "
+                                  "(fused_step=True, obs_format='image', one view group), view 7 at 8-pixel tiles, at most 3 agents, "
+                                  "no 'prestige' agent, grid and atlas in LDS, and for encode_in_step at most 256 object kinds + "
+                                  "agent marks" % what)
 
     def invalidate_obs(self, buffer_set=None):
         """The observation tensors reset() / step() return are views of buffers the env owns and writes again `obs_buffers`

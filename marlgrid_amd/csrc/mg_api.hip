@@ -194,8 +194,10 @@ static int32_t step_render(const MgConfig* cfg, const MgState* st, const void* a
     if (e) return e;
     if (!obs) return MG_E_ARG;      // (every check between the state's and this one answers MG_E_ARG too)
     mg::RenderPick pick;
-    if ((encode_out || ep) && !mg::render_pick(*cfg, ep ? mg::kEpisode : mg::kEncode, &pick)) return MG_E_UNSUPPORTED;
-    if (sig && !mg::render_pick(*cfg, mg::kDelta, &pick)) return MG_E_UNSUPPORTED;
+    if (sig) {      // (mg_step_render_delta; with the encode, the episode outputs or both: mg_step_render_delta_ex)
+        const mg::RenderWant want = encode_out && ep ? mg::kDeltaEncodeEpisode : ep ? mg::kDeltaEpisode : encode_out ? mg::kDeltaEncode : mg::kDelta;
+        if (!mg::render_pick(*cfg, want, &pick)) return MG_E_UNSUPPORTED;
+    } else if ((encode_out || ep) && !mg::render_pick(*cfg, ep ? mg::kEpisode : mg::kEncode, &pick)) return MG_E_UNSUPPORTED;
     const mg::FusedStep fs = fused_step_of(cfg, actions, action_bytes, rewards, auto_reset, encode_out, ep, sig, sig_flags);
     return rc(mg::launch_render(*cfg, *st, obs, nullptr, nullptr, nullptr, (hipStream_t)stream, &fs));
 }
@@ -240,6 +242,14 @@ int32_t mg_step_render_delta(const MgConfig* cfg, const MgState* st, const void*
                              const MgGenProgram* auto_reset, uint8_t* obs, uint16_t* signature, uint32_t flags, void* stream) {
     if (!signature || (flags & ~(uint32_t)MG_DELTA_FORCE) || (reinterpret_cast<uintptr_t>(signature) & 15)) return MG_E_ARG;
     return step_render(cfg, st, actions, action_bytes, rewards, auto_reset, obs, nullptr, stream, nullptr, signature, flags);
+}
+
+int32_t mg_step_render_delta_ex(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,
+                                const MgGenProgram* auto_reset, uint8_t* obs, uint16_t* signature, uint32_t flags,
+                                uint8_t* encode_out, const MgEpisode* ep, void* stream) {
+    if (!signature || (flags & ~(uint32_t)MG_DELTA_FORCE) || (reinterpret_cast<uintptr_t>(signature) & 15)) return MG_E_ARG;
+    if (!encode_out && !ep) return MG_E_ARG;      // (the plain call keeps its one spelling: mg_step_render_delta)
+    return step_render(cfg, st, actions, action_bytes, rewards, auto_reset, obs, encode_out, stream, ep, signature, flags);
 }
 
 int32_t mg_encode(const MgConfig* cfg, const MgState* st, const uint8_t* vis_mask, uint8_t* out, void* stream) {

@@ -13,6 +13,7 @@ extern "C" int mg_ab_stamps(unsigned long long* p) { g_ab_stamps = p; return 0; 
 #if !defined(MG_DEV_ONLY)
 MG_RENDER_ALL(MG_RENDER_EXTERN)
 MG_RENDER_DELTA(MG_RENDER_EXTERN)
+MG_RENDER_DELTA_X(MG_RENDER_EXTERN)
 #endif
 
 using RenderLauncher = hipError_t (*)(const MgConfig&, const MgState&, uint8_t*, uint8_t*, uint8_t*, uint8_t*, hipStream_t,
@@ -23,10 +24,12 @@ static RenderLauncher render_launcher(const RenderPick& p) {
     MG_RENDER_ALL(MG_RENDER_MATCH)
     return nullptr;
 }
-// ... and a kDelta pick in its own list (mg_step_render_delta)
+// ... and a kDelta pick in its own list (mg_step_render_delta), a kDeltaEncode / kDeltaEpisode / kDeltaEncodeEpisode pick in theirs
+// (mg_step_render_delta_ex)
 static RenderLauncher render_delta_launcher(const RenderPick& p) {
 #if !defined(MG_DEV_ONLY)
     MG_RENDER_DELTA(MG_RENDER_MATCH)
+    MG_RENDER_DELTA_X(MG_RENDER_MATCH)
 #endif
     return nullptr;
 }
@@ -68,25 +71,27 @@ static void render_override(const MgConfig& cfg, RenderPick& p) {
 }
 #endif
 
-// The kernel launch of mg_render_obs / mg_step_render / mg_step_render_encode / mg_step_render_ep.
+// The kernel launch of mg_render_obs / mg_step_render / mg_step_render_encode / mg_step_render_ep / mg_step_render_delta[_ex].
 hipError_t launch_render(const MgConfig& cfg, const MgState& st, uint8_t* obs, uint8_t* view_cells,
                          uint8_t* view_agent, uint8_t* vis_mask, hipStream_t s, const FusedStep* fused_step) {
     if (cfg.B <= 0) return hipSuccess;
     FusedStep fs{};                 // no step: the raster alone
     fs.action_bytes = 8;
     if (fused_step) fs = *fused_step;
-    const RenderWant want = fs.has_ep ? kEpisode : fs.encode_out ? kEncode : fs.sig ? kDelta : kPlain;
-    if ((fs.has_ep && fs.encode_out) || (fs.sig && want != kDelta)) return hipErrorInvalidValue;
+    // (the encode AND the episode outputs: under the delta alone — there is no non-delta instantiation with both)
+    const RenderWant want = fs.sig ? (fs.has_ep && fs.encode_out ? kDeltaEncodeEpisode : fs.has_ep ? kDeltaEpisode : fs.encode_out ? kDeltaEncode : kDelta)
+                                   : fs.has_ep ? kEpisode : fs.encode_out ? kEncode : kPlain;
+    if (!fs.sig && fs.has_ep && fs.encode_out) return hipErrorInvalidValue;
     if ((view_cells || view_agent || vis_mask) && (want != kPlain || !(view_cells && view_agent && vis_mask))) return hipErrorInvalidValue;
     RenderPick p;
     if (!render_pick(cfg, want, &p)) return want == kPlain ? hipErrorInvalidValue : hipErrorNotSupported;
-    if (want == kEncode) fs.enc_ne = render_enc_entries(cfg);
+    if (render_want_encode(want)) fs.enc_ne = render_enc_entries(cfg);
 #if defined(MG_AB_VARIANTS) || defined(MG_EXP) || defined(MG_DEV_ONLY)
     render_override(cfg, p);
     if (p.lds > (int)kRenderLdsMax) return hipErrorInvalidValue;
 #endif
     RenderLauncher launch = render_launcher(p);
-    if (!launch && want == kDelta) launch = render_delta_launcher(p);
+    if (!launch && render_want_delta(want)) launch = render_delta_launcher(p);
     if (!launch) return hipErrorInvalidValue;
     return launch(cfg, st, obs, view_cells, view_agent, vis_mask, s, fs, (size_t)p.lds);
 }

@@ -273,6 +273,8 @@ extern unsigned long long* g_ab_stamps;       // set through mg_ab_stamps (mg_re
 //     group's band-mask words take the fused step's columns, which are free once the batch is stepped (the step's LDS-DMA landing
 //     zone moves from the tmap area to the view scratch): no LDS beyond the plain launch's.  Phase 5, a lane per band, compares
 //     and ORs the band's bit into the env's mask; the new signatures go back with stores nobody waits for.
+// VX_ = V_ + 64 + 16 | 32 | 48: mg_step_render_delta_ex's instantiations (MG_RENDER_DELTA_X) — the delta together with the encode,
+//     the episode outputs, or both in ONE launch (the last has no non-delta twin); what shares LDS with what: at the static_assert below.
 template <int VS_, int TS_, int WPB, int VX_ = 0, int RM_ = 0>
 __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState st, uint8_t* __restrict__ obs,
                                                         uint8_t* __restrict__ dbg_cells,
@@ -343,7 +345,31 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
     uint32_t* s_enc = reinterpret_cast<uint32_t*>(s_shared + lc.sh.total + (size_t)WPB * lc.L.total);
     constexpr bool kChunkRaster = TS_ > 0 && (TS_ % 8) == 0 && RM_ == 0;
     constexpr bool kStreamRaster = !kChunkRaster && !kGather;     // assemble-and-stream
-    static_assert(!kDelta || (kChunkRaster && VS_ == 7 && TS_ == 8 && V_ == 0 && !kEnc && !kEp), "mg_step_render_delta: the headline shape's fixed-lane raster");
+    static_assert(!kDelta || (kChunkRaster && VS_ == 7 && TS_ == 8 && V_ == 0), "mg_step_render_delta: the headline shape's fixed-lane raster");
+    // kDelta together with kEp, kEnc or both (mg_step_render_delta_ex: VX_ = 96, 80, 112 — MG_RENDER_DELTA_X).  The delta borrows
+    // LDS from the step — the step's columns (L.step) hold the view group's two tmaps and w_chg once the batch is stepped, the
+    // envs' tmap slots hold the old signatures from the staging loads on — so who else touches what, read off this text:
+    //   * the episode code.  sc.ep points into the kernarg segment, sc.ep_rewards at the rewards in HBM; step_begin reads
+    //     reset_mode, step_par_resolve reads sc.psc (-1: the call is the env's reset), step_end writes out_length / out_flags /
+    //     out_return / ep_return straight to device memory — all inside the stepping region.  The last readers of L.step are
+    //     the write-back of sc.head and sc.rec right behind step_end, in front of the wave_lds_sync that ends the region; the
+    //     first writer of the group's tmaps and of w_chg is phase 1 of the first view group, behind it.  Nothing of StepScratch
+    //     or MgEpisode is looked at later.
+    //   * the encode.  encode_batch runs at the top of the second view group's first iteration (or behind the last group of
+    //     a batch that has one): the first group's rasters are done, its tmaps and w_chg are dead and are rewritten by the
+    //     phase 1 that follows, so it runs between the lives of two groups, not inside one.  encode_batch_mark reads w_stage_r
+    //     and writes agent marks into w_stage_g; encode_batch_chunks reads w_stage_g (a window may run a few bytes past a
+    //     grid, into the next staged grid or the records behind the last: reads) and s_enc and stores to HBM.  Neither touches
+    //     L.step or the tmap slots, where the remaining envs' old signatures wait.  The marks are taken out (undo) before
+    //     phase 1 of the next group reads the grid, exactly as in the plain encode instantiations; behind the last group
+    //     nobody reads the grid again.
+    //   * the LDS-DMA landing zone of the head refills, under delta ws + L.vaff .. ws + L.tmap (the view scratch): used
+    //     inside step_run only, before any view; the encode uses neither it nor anything in it.  s_enc lies behind the LAST
+    //     wave's scratch (the launcher sizes the workgroup's LDS with the table: render_lds_bytes), outside every wave's.
+    //   * next-step reset.  An env whose call is its reset takes the reset path inside step_end like one that resets in the
+    //     same step: `wrote` sends its fresh grid home, its records are staged, and phase 5 compares its bands against the
+    //     signature of the terminal image the buffer set holds (or of whatever it held: the host invalidates on every other
+    //     writer) and stores those that differ.  No special case.
     // the rasters bound by instruction issue run at a raised wave priority (phase 6); measured per instantiation: the gather
     // raster at 11-pixel tiles without 'prestige' agents is close enough to the HBM bound to lose 0.6 % by it
     constexpr bool kRasterPrio = (kGather && (TS_ <= 10 || V_ == 9)) || kStreamRaster;

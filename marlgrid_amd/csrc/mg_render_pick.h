@@ -197,8 +197,12 @@ struct RenderPick { int vs, ts, wpb, v, rm, lds; };
 // what the launch has to do besides the raster: nothing (mg_render_obs, mg_step_render), MultiGrid.encode of the stepped batch
 // (mg_step_render_encode: the instantiations V + 16, MG_RENDER_GROUP_N), the episode outputs (mg_step_render_ep: V + 32, group P)
 // ... or the band-wise comparison against the signature of what the output buffer already holds (mg_step_render_delta: V + 64,
-// MG_RENDER_DELTA — a list of its own, not part of MG_RENDER_ALL)
-enum RenderWant { kPlain, kEncode, kEpisode, kDelta };
+// MG_RENDER_DELTA — a list of its own, not part of MG_RENDER_ALL) ... or that comparison TOGETHER with the encode, the episode
+// outputs or both (mg_step_render_delta_ex: V + 64 + 16 | 32 | 48, MG_RENDER_DELTA_X — a second list of its own)
+enum RenderWant { kPlain, kEncode, kEpisode, kDelta, kDeltaEncode, kDeltaEpisode, kDeltaEncodeEpisode };
+constexpr bool render_want_delta(RenderWant w) { return w >= kDelta; }
+constexpr bool render_want_encode(RenderWant w) { return w == kEncode || w == kDeltaEncode || w == kDeltaEncodeEpisode; }
+constexpr bool render_want_episode(RenderWant w) { return w == kEpisode || w == kDeltaEpisode || w == kDeltaEncodeEpisode; }
 
 // dwords of the fused encode's LDS table — one per grid byte value, (n_obj + 4 n) rounded up to 16 —, 0: object ids and
 // agent marks do not share a byte, no fused encode
@@ -311,11 +315,11 @@ inline bool render_pick(const MgConfig& cfg, RenderWant want, RenderPick* out) {
         // Not: a grid read in place, 'prestige' agents, an atlas in global memory (all V != 0).
         const bool shape = p.v == 0 && ((p.rm == 2 && p.vs == 7 && p.ts == 5) ||
                                         (p.rm == 0 && p.ts == 8 && (p.vs == 7 || p.vs == 9 || (p.vs == 0 && vs > 9))));
-        // (mg_step_render_delta: the headline shape alone — view 7 at 8-pixel tiles, the fixed-lane chunk raster — with few enough
-        // agents for render_delta_fits)
-        if (want == kDelta ? !(shape && p.rm == 0 && p.vs == 7 && render_delta_fits(cfg, render_scratch_for(cfg, p.wpb, 0))) : !shape) return false;
-        p.v |= want == kEncode ? 16 : want == kEpisode ? 32 : 64;
-        if (want == kEncode) {
+        // (mg_step_render_delta, mg_step_render_delta_ex: the headline shape alone — view 7 at 8-pixel tiles, the fixed-lane chunk
+        // raster — with few enough agents for render_delta_fits; what it asks of a wave's layout does not depend on the workgroup)
+        if (render_want_delta(want) ? !(shape && p.rm == 0 && p.vs == 7 && render_delta_fits(cfg, render_scratch_for(cfg, p.wpb, 0))) : !shape) return false;
+        p.v |= (render_want_encode(want) ? 16 : 0) | (render_want_episode(want) ? 32 : 0) | (render_want_delta(want) ? 64 : 0);
+        if (render_want_encode(want)) {
             // the encode's table has to fit beside FOUR waves of scratch, whatever the batch: render_scratch_for fills LDS with staged
             // envs, so a larger workgroup's leaner layout may fit where this one does not — such a configuration has no fused encode
             enc_ne = render_enc_entries(cfg);
@@ -347,7 +351,7 @@ inline bool render_pick(const MgConfig& cfg, RenderWant want, RenderPick* out) {
 inline bool render_pick_ideal(const MgConfig& cfg, RenderWant want, RenderPick* out) {
     const int vs = cfg.view_size, ts = cfg.tile_size;
     RenderPick plain;
-    if (want == kDelta || vs < 3 || vs > MG_MAX_VIEW || !render_pick(cfg, kPlain, &plain) || plain.v != 0) return false;
+    if (render_want_delta(want) || vs < 3 || vs > MG_MAX_VIEW || !render_pick(cfg, kPlain, &plain) || plain.v != 0) return false;
     RenderPick p = {vs, 0, 4, 0, 0, 0};
     if (ts >= 5 && ts % 8 != 0 && gather_trips(vs, ts) <= 4 && render_fits(cfg, 4, 2)) { p.ts = ts; p.rm = 2; }
     else if (!render_fits(cfg, 4, 0)) return false;
@@ -429,6 +433,11 @@ inline bool render_pick_ideal(const MgConfig& cfg, RenderWant want, RenderPick* 
 // mg_step_render_delta (V + 64): NOT part of MG_RENDER_ALL — the launcher looks a kDelta pick up in this list (inst group Q)
 #define MG_RENDER_DELTA(X) X(7, 8, 16, 64, 0) X(7, 8, 4, 64, 0)
 #define MG_RENDER_GROUP_Q(X) MG_RENDER_DELTA(X)
+// mg_step_render_delta_ex (V + 64 + 16: with the encode, + 32: with the episode outputs, + 48: with both): not part of MG_RENDER_ALL
+// either — the launcher looks a kDeltaEncode / kDeltaEpisode / kDeltaEncodeEpisode pick up in this list (inst group R)
+#define MG_RENDER_DELTA_X(X)                                                                                               \
+    X(7, 8, 16, 96, 0) X(7, 8, 4, 96, 0) X(7, 8, 16, 80, 0) X(7, 8, 4, 80, 0) X(7, 8, 16, 112, 0) X(7, 8, 4, 112, 0)
+#define MG_RENDER_GROUP_R(X) MG_RENDER_DELTA_X(X)
 // every instantiation of this build (the headline shape's group first: the launcher's lookup walks the list in order)
 #if defined(MG_DEV_ONLY)      // development: compile ONE instantiation (register / ISA checks without the other hundred), e.g. -DMG_DEV_ONLY="7,5,16,0,0"
 #define MG_RENDER_ONE(X, ...) X(__VA_ARGS__)

@@ -1,0 +1,234 @@
+"""obs_delta together with episode outputs and the grid encoding, without a GPU: the launcher's pick for mg_step_render_delta_ex
+— the g++ build of marlgrid_amd/csrc/mg_render_pick.h (tests/native/mg_obs_delta_ex.cpp) — over every configuration of the
+recorded table tests/golden/render_picks.npz.  The three new wants are answered exactly where the delta pick is (with the encode:
+where the recorded encode pick is, too), with the workgroup and the LDS bytes of the recorded episode / encode pick, V = 64 + 32 |
+16 | 48; every answer is an entry of MG_RENDER_DELTA_X, a list disjoint from MG_RENDER_ALL and MG_RENDER_DELTA, which are what
+they were.  Then the built library's entry point on an empty batch (every check is made, nothing is launched), and the host's
+bookkeeping on dry envs.
+
+(That the kernels compute the right bytes is held on the GPU: tests/test_hip_obs_delta_ex.py.)"""
+import ctypes as C
+import fcntl
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from marlgrid_amd import _native as N
+
+import test_render_pick as TRP
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+NATIVE = os.path.join(HERE, "native")
+CSRC = os.path.join(os.path.dirname(HERE), "marlgrid_amd", "csrc")
+NAME = "MarlGrid-3AgentCluttered15x15-v0"
+
+DELTA_X = {(7, 8, 16, 96, 0), (7, 8, 4, 96, 0), (7, 8, 16, 80, 0), (7, 8, 4, 80, 0), (7, 8, 16, 112, 0), (7, 8, 4, 112, 0)}
+# want -> (its V, the recorded want whose workgroup and LDS it has: 1 encode, 2 episode — tests/test_render_pick.py WANTS)
+WANTS = {4: (80, 1), 5: (96, 2), 6: (112, 1)}
+
+
+@pytest.fixture(scope="module")
+def dx_lib():
+    out = os.path.join(NATIVE, "libmg_obs_delta_ex.so")
+    with open(os.path.join(NATIVE, ".build.lock"), "w") as lock:        # (one builder at a time, as tests/native/hostemu.py)
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-Wno-unused-function",
+                               "-I", os.path.join(os.path.dirname(HERE), "include"), "-I", CSRC,
+                               os.path.join(NATIVE, "mg_obs_delta_ex.cpp"), "-o", out])
+    L = C.CDLL(out)
+    assert L.dx_sizeof_config() == C.sizeof(N.Config)
+    return L
+
+
+@pytest.fixture(scope="module")
+def table():
+    d = np.load(os.path.join(HERE, "golden", "render_picks.npz"))
+    cols = [str(c) for c in d["cfg_cols"]]
+    return {c: d["cfg"][:, i] for i, c in enumerate(cols)}, d["pick"].reshape(len(d["cfg"]), -1)
+
+
+def delta_rows(cfg, pick):
+    """where the delta pick is answered, from the recorded plain pick (the rule tests/test_obs_delta_host.py holds kDelta to)"""
+    plain = pick[:, 2:9]
+    shape = (plain[:, 0] == 1) & (plain[:, 1] == 7) & (plain[:, 2] == 8) & (plain[:, 4] == 0) & (plain[:, 5] == 0)
+    return shape & (cfg["n_view"] == 0) & (cfg["n_agents"] <= 3) & (cfg["prestige_mask"] == 0)
+
+
+def listed(dx_lib, which):
+    buf = (C.c_int32 * (5 * 256))()
+    n = dx_lib.dx_list(which, buf, 256)
+    assert 0 < n <= 256
+    out = [tuple(buf[5 * k:5 * k + 5]) for k in range(n)]
+    assert len(set(out)) == n, "an instantiation is listed twice"
+    return set(out)
+
+
+def test_new_wants_are_appended(dx_lib):
+    v = (C.c_int32 * 4)()
+    dx_lib.dx_want_values(v)
+    assert list(v) == [3, 4, 5, 6]
+
+
+def test_lists(dx_lib, table):
+    cfg, pick = table
+    x, delta, every = listed(dx_lib, 0), listed(dx_lib, 1), listed(dx_lib, 2)
+    assert x == DELTA_X
+    assert delta == {(7, 8, 16, 64, 0), (7, 8, 4, 64, 0)}
+    assert not x & every and not x & delta and not delta & every
+    # MG_RENDER_ALL: what the recorded table picks and the four entries nothing reaches (tests/test_render_pick.py)
+    picked = set()
+    for w in range(3):
+        rows = pick[pick[:, 2 + 7 * w] == 1]
+        picked |= {tuple(r) for r in rows[:, 3 + 7 * w:8 + 7 * w].tolist()}
+    assert every == picked | TRP.UNREACHED
+
+
+@pytest.mark.parametrize("want", sorted(WANTS))
+def test_pick_over_the_recorded_table(dx_lib, table, want):
+    cfg, pick = table
+    v, like = WANTS[want]
+    n = len(pick)
+    cfgs = (N.Config * n)()
+    for i in range(n):
+        TRP.fill(cfgs[i], cfg, i)
+    out = np.zeros((n, 7), np.int32)
+    dx_lib.dx_rows(cfgs, n, want, C.c_void_p(out.ctypes.data))
+    rec = pick[:, 2 + 7 * like:9 + 7 * like]               # picked, vs, ts, wpb, v, rm, lds of the recorded non-delta want
+    delta = delta_rows(cfg, pick)
+    answered = delta & (pick[:, 9] == 1) if want in (4, 6) else delta
+    assert answered.sum() >= 20 and (~answered).sum() >= 20, (answered.sum(), (~answered).sum())
+    assert np.array_equal(out[:, 0] == 1, answered), np.nonzero((out[:, 0] == 1) != answered)[0][:10]
+    assert (rec[answered, 0] == 1).all()                   # (where the delta is answered the episode pick is, too)
+    got = out[answered]
+    assert (got[:, 1] == 7).all() and (got[:, 2] == 8).all() and (got[:, 4] == v).all() and (got[:, 5] == 0).all()
+    assert np.array_equal(got[:, 3], rec[answered, 3])     # the non-delta launch's workgroup ...
+    assert np.array_equal(got[:, 6], rec[answered, 6])     # ... and not a byte of LDS more
+    assert {tuple(r) for r in got[:, 1:6].tolist()} <= DELTA_X
+    assert set(got[:, 3].tolist()) == {4, 16}
+
+
+def test_first_four_wants_unchanged(dx_lib, table):
+    cfg, pick = table
+    TRP.test_render_pick_answers_the_recorded_table(table, TRP.load_pick_lib())
+    n = len(pick)
+    cfgs = (N.Config * n)()
+    for i in range(n):
+        TRP.fill(cfgs[i], cfg, i)
+    out = np.zeros((n, 7), np.int32)
+    dx_lib.dx_rows(cfgs, n, 3, C.c_void_p(out.ctypes.data))
+    delta = delta_rows(cfg, pick)
+    assert np.array_equal(out[:, 0] == 1, delta)
+    assert (out[delta, 4] == 64).all() and np.array_equal(out[delta, 6], pick[delta, 8])
+
+
+def test_library_on_an_empty_batch(table):
+    """the C entry point with B = 0: every check is made, nothing is launched"""
+    cfg, pick = table
+    L = N.lib()
+    keep = C.create_string_buffer(64)
+    p = (C.addressof(keep) + 15) & ~15
+    st = N.State(*([p] * 10))
+    c = N.Config()
+    ep = N.Episode()
+    delta = delta_rows(cfg, pick)
+    rows = [i for i in range(len(pick)) if cfg["n_view"][i] == 0]
+    rows = rows[::7] + [i for i in rows if delta[i]][:50] + [i for i in rows if delta[i] and not pick[i, 9]][:10]
+    seen = {}
+    for i in rows:
+        TRP.fill(c, cfg, i, B=0)
+        for enc, e in ((p, None), (None, C.byref(ep)), (p, C.byref(ep))):
+            ok = delta[i] and (enc is None or pick[i, 9] == 1)
+            rc = L.mg_step_render_delta_ex(C.byref(c), C.byref(st), p, 8, p, None, p, p, N.DELTA_FORCE, enc, e, None)
+            assert rc == (N.OK if ok else N.E_UNSUPPORTED), (i, enc is not None, e is not None, rc)
+            seen.setdefault((enc is not None, e is not None), set()).add(rc)
+        # ... and the plain call answers as before
+        rc = L.mg_step_render_delta(C.byref(c), C.byref(st), p, 8, p, None, p, p, N.DELTA_FORCE, None)
+        assert rc == (N.OK if delta[i] else N.E_UNSUPPORTED), (i, rc)
+    assert all(v == {N.OK, N.E_UNSUPPORTED} for v in seen.values()) and len(seen) == 3, seen
+    i = next(i for i in rows if delta[i] and pick[i, 9])
+    TRP.fill(c, cfg, i, B=0)
+    head = (C.byref(c), C.byref(st), p, 8, p, None, p)
+    assert L.mg_step_render_delta_ex(*head, p, 0, p, C.byref(ep), None) == N.OK
+    assert L.mg_step_render_delta_ex(*head, p, 0, None, None, None) == N.E_ARG               # both extras NULL
+    assert L.mg_step_render_delta_ex(*head, None, 0, p, C.byref(ep), None) == N.E_ARG        # no signature
+    assert L.mg_step_render_delta_ex(*head, p + 2, 0, p, C.byref(ep), None) == N.E_ARG       # misaligned
+    assert L.mg_step_render_delta_ex(*head, p, 2, p, C.byref(ep), None) == N.E_ARG           # unknown flag
+    # an MgEpisode check_episode refuses: an unknown reset mode; next-step reset without a program; out_return without ep_return
+    for bad in (N.Episode(2, 0, None, None, None, None), N.Episode(N.RESET_NEXT_STEP, 0, None, None, None, None),
+                N.Episode(N.RESET_SAME_STEP, 0, None, p, None, None)):
+        assert L.mg_step_render_delta_ex(*head, p, 0, None, C.byref(bad), None) == N.E_ARG
+        assert L.mg_step_render_delta_ex(*head, p, 0, p, C.byref(bad), None) == N.E_ARG
+
+
+def test_symbol_is_declared():
+    assert "mg_step_render_delta_ex" in N.SYMBOLS
+    with open(os.path.join(os.path.dirname(HERE), "include", "marlgrid_hip.h")) as f:
+        assert "int32_t mg_step_render_delta_ex(" in f.read()
+    assert N.ABI_VERSION == 6
+
+
+MIXES = [dict(episode_info=True), dict(auto_reset="next_step"), dict(encode_in_step=True),
+         dict(encode_in_step=True, auto_reset="next_step", episode_info=True)]
+
+
+def test_auto_stays_off_with_episode_outputs():
+    from marlgrid_amd.envs import make
+    for kw in MIXES:
+        env = make(NAME, batch_size=2, obs_delta="auto", _dry=True, **kw)
+        assert not env._delta_wanted(), kw
+    assert make(NAME, batch_size=2, obs_delta="auto", _dry=True)._delta_wanted()
+    assert not make(NAME, batch_size=2, obs_delta=False, _dry=True, episode_info=True)._delta_wanted()
+
+
+@pytest.mark.parametrize("kw", MIXES, ids=["episode_info", "next_step", "encode_in_step", "all"])
+def test_true_is_wanted_with_every_mix(kw):
+    from marlgrid_amd.envs import make
+    env = make(NAME, batch_size=2, obs_delta=True, _dry=True, **kw)
+    assert env._delta_wanted()
+    assert env._use_ep == ("episode_info" in kw or "auto_reset" in kw)
+    env.invalidate_obs()                # (a dry env has no ring: nothing to do, no error)
+
+
+class _Ptr:
+    def data_ptr(self):
+        return 64
+
+
+class _Refuses:
+    calls = 0
+
+    def mg_step_render_delta_ex(self, *a):
+        self.calls += 1
+        return N.E_UNSUPPORTED
+
+
+def test_true_raises_where_the_library_has_no_instantiation():
+    """view_tile_size=5 + episode_info: what is pinned is where the error comes — not at construction (the library is the one
+    that knows its table, and a dry env never asks it), at the first step: MG_E_UNSUPPORTED from mg_step_render_delta_ex is a
+    NotImplementedError that names what is needed, and the env does not ask again"""
+    from marlgrid_amd.envs import ClutteredMultiGrid
+    agents = [dict(view_size=7, view_tile_size=5, observation_style="image", color=c) for c in ("red", "blue", "purple")]
+    env = ClutteredMultiGrid(agents=agents, grid_size=15, n_clutter=20, batch_size=2, obs_delta=True, episode_info=True, _dry=True)
+    assert env.tile_size == 5 and env._delta_wanted()          # construction: no error, nobody has said no yet
+    env._lib, env._ring, env._ring_i, env.obs, env._delta_launches = _Refuses(), [dict(sig=_Ptr())], 0, _Ptr(), 0
+    with pytest.raises(NotImplementedError, match="episode outputs.*8-pixel tiles"):
+        env._launch_step_delta_ex((None,) * 6, C.byref(N.Episode()), None)
+    assert env._lib.calls == 1 and not env._delta_wanted() and env._ring[0]["sig"] is None and env._delta_launches == 0
+    with pytest.raises(NotImplementedError):
+        env._launch_step_delta_ex((None,) * 6, C.byref(N.Episode()), None)
+    assert env._lib.calls == 1
+
+
+@pytest.mark.parametrize("kw", [dict(fused_step=False), dict(obs_format="encoded")], ids=["two_launches", "encoded_views"])
+def test_true_raises_off_the_fused_image_step(kw):
+    """obs_delta=True with episode outputs is a demand everywhere: an env whose step is not the fused image launch raises at its
+    first step instead of stepping without the delta, and asks the library nothing"""
+    from marlgrid_amd.envs import make
+    env = make(NAME, batch_size=2, obs_delta=True, episode_info=True, _dry=True, **kw)
+    assert not env._delta_wanted()
+    env._lib, env._ring, env._ring_i, env.obs, env._delta_launches = _Refuses(), [dict(sig=None)], 0, _Ptr(), 0
+    with pytest.raises(NotImplementedError, match="fused image step"):
+        env._launch_step_delta_ex((None,) * 6, C.byref(N.Episode()), None)      # (what _launch_step calls for this env: GPU test)
+    assert env._lib.calls == 0

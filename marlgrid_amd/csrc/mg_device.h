@@ -107,6 +107,7 @@ struct RenderLaunch {
     RenderShared sh;                            // the block-shared tables behind it (render_shared_layout)
 #if defined(MG_AB_VARIANTS)
     unsigned long long* stamps;                 // measurement build: phase stamps of every wave (tools/phase_stamps.py), or null
+    int prio_mode;                              // measurement build: the delta launch's wave-priority policy (kDeltaPrio*, mg_render_kernel.h)
 #endif
 };
 

@@ -250,6 +250,30 @@ extern unsigned long long* g_ab_stamps;       // set through mg_ab_stamps (mg_re
 #define MG_STAMP(slot) do {} while (0)
 #endif
 
+// ---- mg_step_render_delta: the waves' issue priority ---------------------------------------------------
+// A SIMD arbitrates between its four waves by priority, then age.  With every wave at priority 0 the plain tile-8 launch's
+// waves exit in tiers, one per wave slot of the SIMD (profiles/r06/wave_exit_by_slot_v15.txt) — free while the launch is
+// HBM-bound, whoever issues the stores.  The delta launch is not (profiles/obs_delta): a SIMD whose older waves are gone
+// alternates a store-free view phase with a half-empty raster.  The policies (profiles/obs_delta_priority/README.md):
+//   kDeltaPrioProgress        delta_wave_prio (mg_step_layout.h) of the wave's finished view groups, set when a group begins:
+//                             the wave that is behind out-ranks the wave that is ahead; all start at 3 (age decides the head)
+//   kDeltaPrioRaster          kRasterPrio's form: 3 in the raster, 0 in the views
+//   kDeltaPrioProgressRaster  the group's value, the raster one level above it (at most 3)
+// s_setprio changes the order of issue and nothing else: no state between waves, the outputs are the same bytes.  The product
+// compiles ONE in (kDeltaPrioShipped); the measurement build takes it from the launch (RenderLaunch::prio_mode).
+enum { kDeltaPrioOff = 0, kDeltaPrioProgress = 1, kDeltaPrioRaster = 2, kDeltaPrioProgressRaster = 3 };
+constexpr int kDeltaPrioShipped = kDeltaPrioProgress;
+// s_setprio takes an immediate: the (wave-uniform) value picks one of four — as an SGPR, so that the switch is scalar
+// branches around ONE s_setprio each (the instruction ignores EXEC: under a per-lane guard every wave would run it)
+__device__ __forceinline__ void wave_setprio(int p) {
+    switch (__builtin_amdgcn_readfirstlane(p)) {
+    case 0: __builtin_amdgcn_s_setprio(0); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+    }
+}
+
 // ---- the kernel ----------------------------------------------------------------------------------
 // TS_ % 8 == 0: 16-byte-chunk fast raster (tile rows are an even number of dwords); VS_ > 0 also
 //              fixes the view size at compile time (the shipped view sizes), VS_ == 0 reads it from cfg.
@@ -439,6 +463,23 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
     // item -> (slot, rest), view cell -> (viewer, row, column): 24-bit multiplies only (Div20; MG_REGION_LOCALS)
     constexpr bool kExactVV = VS_ > 0 && VS_ <= 9;     // 16 viewers * VS^2 cells: x * (m*d - 2^20) < 2^20 holds (checked below)
     static_assert(VS_ == 0 || VS_ > 9 || (16u * VS_ * VS_ * ((((1u << 20) + VS_ * VS_ - 1u) / (VS_ * VS_)) * (VS_ * VS_) - (1u << 20)) < (1u << 20)), "Div20 exactness");
+    // (mg_step_render_delta) the wave's priority policy, and its progress in view groups over its WHOLE run: full batches of
+    // K envs in groups of `depth`, then the rest.  Every wave enters its first pass at 3.
+#if defined(MG_AB_VARIANTS)
+    const int prio_mode = kDelta ? lc.prio_mode : kDeltaPrioOff;
+#else
+    constexpr int prio_mode = kDelta ? kDeltaPrioShipped : kDeltaPrioOff;
+#endif
+    int prio_done = 0, prio_total = 1, prio_cur = 0;
+    if constexpr (kDelta) {
+        if (prio_mode & kDeltaPrioProgress) {
+            const int ne = max(0, e_end - e0), full = ne / K, rest = ne - full * K;
+            prio_total = full * ((K + depth - 1) / depth) + (rest + depth - 1) / depth;
+            prio_cur = 3;
+            __builtin_amdgcn_s_setprio(3);
+        }
+    }
+    (void)prio_done; (void)prio_total; (void)prio_cur;
 
     for (int eb = e0; ; eb += K) {
         const bool first = (eb == e0);
@@ -867,6 +908,13 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
             }
         for (int i = lane; i < G * L.trow_stride; i += kWave) w_trow[i] = 0;
         if constexpr (kDelta) { if (lane < 2) w_chg[lane] = 0; }
+        if constexpr (kDelta) {       // a view group begins: the wave's priority by the groups it has behind it
+            if (prio_mode & kDeltaPrioProgress) {
+                prio_cur = delta_wave_prio(prio_done, prio_total);
+                wave_setprio(prio_cur);
+                prio_done++;
+            }
+        }
         wave_lds_sync();
         if constexpr (V_ == 3 || V_ == 4) {
             for (int g = 0; g < G; g++)
@@ -1185,6 +1233,10 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
         // less often (whole step: tile 5 -4.2 %, tile 6 -1.2 %, view 9 at tile 5 -3.8 %, tile 13 — assemble-and-stream — -4.7 %,
         // the reference's example -1.8 %; tile 8, HBM-bound: +0.01 %, tile 11: +0.6 % — both left alone; profiles/r05).
         if constexpr (kRasterPrio) __builtin_amdgcn_s_setprio(3);
+        if constexpr (kDelta) {       // (the measured alternatives: the raster raised, over 0 or over the group's value)
+            if (prio_mode == kDeltaPrioRaster) __builtin_amdgcn_s_setprio(3);
+            else if (prio_mode == kDeltaPrioProgressRaster) wave_setprio(min(3, prio_cur + 1));
+        }
         if constexpr (kGather) {
             // the whole GROUP's images as one stream (mg_gather.h), when the group's first env comes up — or, 'prestige', env
             // by env: the recoloured tiles (w_dyn: ONE slot, virtual tiles >= NT4) are this env's
@@ -1491,6 +1543,10 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
         }
         }
         if constexpr (kRasterPrio) __builtin_amdgcn_s_setprio(0);
+        if constexpr (kDelta) {
+            if (prio_mode == kDeltaPrioRaster && pass == 1) __builtin_amdgcn_s_setprio(0);
+            else if (prio_mode == kDeltaPrioProgressRaster && pass == 1) wave_setprio(prio_cur);
+        }
         wave_lds_sync();   // scratch is reused by the next env
         if (e == e0) MG_STAMP(pass == 0 ? 4 : 5);
     }
@@ -1557,6 +1613,9 @@ inline int render_launch_plan(const MgConfig& cfg, int wpb, int vx, int rm, size
 #if defined(MG_AB_VARIANTS)
     lc.stamps = g_ab_stamps;
     if (const char* f = getenv("MG_RENDER_DEPTH")) lc.depth_mode = atoi(f);   // 1: every wave view -> raster env by env
+    // the delta launch's wave priorities: 0 none, 1 by progress, 2 raster raised, 3 both (kDeltaPrio*); unset: the product's
+    lc.prio_mode = kDeltaPrioShipped;
+    if (const char* f = getenv("MG_RENDER_PRIO")) { const int v = atoi(f); if (v >= kDeltaPrioOff && v <= kDeltaPrioProgressRaster) lc.prio_mode = v; }
 #endif
     *out = lc;
     return blocks;

@@ -68,4 +68,16 @@ MG_LAYOUT_FN FusedStepLayout fused_step_layout(int n) {
 }
 MG_LAYOUT_FN size_t fused_step_bytes(int n) { return (size_t)fused_step_layout(n).total; }
 
+// mg_step_render_delta: the issue priority (s_setprio, 0 .. 3) of a wave that has finished `groups_done` of the `groups_total`
+// view groups of its WHOLE run of envs (all its staged batches, not one batch).  A SIMD arbitrates between its waves by
+// priority, then age: with every wave at 0 the oldest wave of a SIMD runs unimpeded and the youngest takes what is left.
+// Ordered by progress, the wave that is behind out-ranks the wave that is ahead.  3 with nothing done, never rising, four
+// levels spread evenly over the run: 3 - min(3, 4 * done / total) — 3, 2, 1, 0 for the bench shape's four groups.
+MG_LAYOUT_FN int delta_wave_prio(int groups_done, int groups_total) {
+    if (groups_done <= 0 || groups_total <= 0) return 3;
+    if (groups_done >= groups_total) return 0;           // (below: done < total, the groups of ONE wave's run)
+    const int q = 4 * groups_done / groups_total;          // 0 .. 3
+    return 3 - q;
+}
+
 }  // namespace mg

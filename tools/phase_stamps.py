@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Where does a wave of the fused launch spend its time before its first store?  Measurement build: every wave
 stamps wall_clock64 (100 MHz) at the phase boundaries of its first batch (mg_render.hip, MG_STAMP); this prints
-the per-phase durations over all waves of one mg_step_render launch (and of one mg_render_obs launch)."""
+the per-phase durations over all waves of one mg_step_render launch (and of one mg_render_obs launch), the waves' exit and
+first-store times by their place in the workgroup (waves w, w + 4, ... share a SIMD) and by the SIMD the hardware names.
+OBS_DELTA=1: the delta launch instead (obs_delta=True, two buffer sets, REPS steps of env.step() after 40 warm-up steps);
+MG_RENDER_PRIO=0..3 picks its wave-priority policy in the measurement build (mg_render_kernel.h, kDeltaPrio*)."""
 import ctypes as C
 import os
 import sys
@@ -27,6 +30,9 @@ elif os.environ.get("PRESTIGE"):    # PRESTIGE=<agents>,<tile>: the goal-cycle s
         agents=[GridAgentInterface(color="prestige", view_size=7, view_tile_size=_ts, view_offset=1) for _ in range(_n)],
         grid_size=13, clutter_density=0.15, n_bonus_tiles=3, max_steps=250, respawn=True, reward_decay=False,
         initial_reward=True, penalty=-1.5, batch_size=B, strict=False, auto_reset=True)
+elif os.environ.get("OBS_DELTA"):   # the delta launch (mg_step_render_delta) in steady state: env.step() itself, two buffer sets
+    env = make(os.environ.get("WL", "MarlGrid-3AgentCluttered15x15-v0"), batch_size=B, auto_reset=True, strict=False,
+               obs_delta=True, obs_buffers=2)
 else:
     env = make(os.environ.get("WL", "MarlGrid-3AgentCluttered15x15-v0"), batch_size=B, auto_reset=True, strict=False)
 env.reset()
@@ -35,6 +41,9 @@ acts = [torch.randint(0, 7, (B, env.num_agents), generator=g).cuda() for _ in ra
 for i in range(40):
     env.step(acts[i % 16])
 L, cfg, st = env._lib, C.byref(env._cfg), C.byref(env._state)
+WPB = int(env.kernel_name.split(",")[2])      # waves per workgroup of the step's instantiation: mg::render_kernel<VS, TS, WPB, V, RM>
+print("%s, %d envs, %s%s" % (env.kernel_name, B, L.mg_build_info().decode() if hasattr(L, "mg_build_info") else "",
+                             ", MG_RENDER_PRIO=%s" % os.environ["MG_RENDER_PRIO"] if os.environ.get("MG_RENDER_PRIO") else ""))
 stamps = torch.zeros(65536 * 24, dtype=torch.int64, device="cuda")
 names = ["tables + atlas -> LDS, barrier", "stage grids (+ step_load)", "step_run (+ records, write-back)",
          "views of the first group", "raster of the first env", "rest of the run"]
@@ -47,6 +56,7 @@ def report(title):
         import numpy as np
         np.save(os.path.join(os.environ["STAMPS_OUT"], "stamps_%s_%d.npy" % (title, report.n)), t[t[:, 6] != 0].numpy())
         report.n += 1
+    hw = t[t[:, 6] != 0][:, 7]                    # XCC_ID << 16 | HW_ID
     t = t[t[:, 6] != 0].double() / 100.0          # us
     t0 = t[:, 0].min()
     print("%s: %d waves; first entry -> last exit %.1f us; entry skew %.1f us" %
@@ -64,6 +74,26 @@ def report(title):
     print("   mean exit time by XCD (workgroup %% 8): %s" % " ".join("%.1f" % v for v in by_xcd))
     by_wave = [ex[torch.arange(len(ex)) % 4 == w].mean().item() for w in range(4)]
     print("   mean exit time by look-ahead depth 1/2/4/8 (wave %% 4): %s" % " ".join("%.1f" % v for v in by_wave))
+    if WPB:
+        # By the wave's place in its workgroup: waves w, w + 4, w + 8, w + 12 of a 16-wave workgroup share a SIMD, and the SIMD
+        # arbitrates by priority, then age — `slot` = index // 4 is the wave's age rank on its SIMD.  Then by what the hardware
+        # says (stamp 7, HW_ID: wave slot [3:0], SIMD [5:4]).
+        idx = torch.arange(len(ex))
+        print("   workgroups of %d waves; mean exit by wave index: %s" % (WPB, " ".join("%.1f" % ex[idx % WPB == w].mean().item() for w in range(WPB))))
+        nslot = max(1, WPB // 4)
+        for nm, x in (("exit", ex), ("first views done (first store)", fs)):
+            print("   %-31s by slot (index // 4): %s" % (nm, "  ".join(
+                "%d: mean %.1f p10 %.1f p90 %.1f max %.1f" % ((s,) + tuple(f(x[(idx % WPB) // 4 == s]).item() for f in (
+                    torch.mean, lambda v: torch.quantile(v, 0.1), lambda v: torch.quantile(v, 0.9), torch.max))) for s in range(nslot))))
+        print("   mean exit by SIMD (HW_ID [5:4]): %s;  by index %% 4: %s" % (
+            " ".join("%.1f" % ex[((hw >> 4) & 3) == s].mean().item() for s in range(4) if (((hw >> 4) & 3) == s).any()),
+            " ".join("%.1f" % ex[idx % 4 == s].mean().item() for s in range(4))))
+        wg = ex[:len(ex) // WPB * WPB].view(-1, WPB)
+        print("   spread inside a workgroup (max - min exit): mean %.1f  max %.1f us;  workgroup mean exit %.1f .. %.1f us" %
+              ((wg.max(1).values - wg.min(1).values).mean().item(), (wg.max(1).values - wg.min(1).values).max().item(),
+               wg.mean(1).min().item(), wg.mean(1).max().item()))
+        print("   first store: earliest wave %.2f us, spread (max - min) %.1f us, p90 - p10 %.1f us" %
+              (fs.min().item(), (fs.max() - fs.min()).item(), (torch.quantile(fs, 0.9) - torch.quantile(fs, 0.1)).item()))
     if (t[:, 13] != 0).any():
         for nm, x, y in (("entry -> launch constants set up", 0, 13), ("-> env loop entered (hoisted invariants)", 13, 14),
                          ("prologue's loads issued and back", 14, 15), ("LDS stores + barrier", 15, 1)):
@@ -89,7 +119,14 @@ def report(title):
 report.n = 0
 L.mg_ab_stamps.restype = C.c_int
 assert L.mg_ab_stamps(C.c_void_p(stamps.data_ptr())) == 0
-for rep in range(2):
+if os.environ.get("OBS_DELTA"):
+    # env.step() is the launch: 40 warm-up steps are behind it (20 per buffer set: both signatures are valid), uniform actions
+    before = env._delta_launches
+    for rep in range(int(os.environ.get("REPS", "4"))):
+        env.step(acts[(8 + rep) % 16])
+        report("mg_step_render_delta")
+    assert env._delta_wanted() and env._delta_launches - before == int(os.environ.get("REPS", "4"))
+for rep in range(0 if os.environ.get("OBS_DELTA") else 2):
     N.check(L.mg_step_render(cfg, st, acts[rep].data_ptr(), 8, env.rewards.data_ptr(), C.byref(env._reset_prog),
                              env.obs.data_ptr(), env._stream()))
     report("mg_step_render")

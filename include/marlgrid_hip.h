@@ -79,6 +79,11 @@ extern "C" {
 #define MG_GEN_SYM 0x40000000     /* an operand x0/y0/x1/y1 with this bit is `const +- draw[r]`, not a plain integer: */
 #define MG_GEN_NEG 0x20000000     /*   set: const - draw[r]; clear: const + draw[r] */
 #define MG_GEN_DRAW_SHIFT 16      /*   r = (operand >> 16) & 7; const = (int16_t)(operand & 0xFFFF) */
+/* the guard of a reset-program op, in the upper bits of MgGenOp.obj (values that were illegal before: ABI 6 still) */
+#define MG_GEN_GUARD 0x40000000   /* the op runs only if lo <= draw[r] <= hi (lo <= hi); else it is skipped entirely */
+#define MG_GEN_GUARD_DRAW_SHIFT 24 /*   r = (obj >> 24) & 7 */
+#define MG_GEN_GUARD_HI_SHIFT 16  /*   hi = (obj >> 16) & 0xFF */
+#define MG_GEN_GUARD_LO_SHIFT 8   /*   lo = (obj >> 8) & 0xFF; the low byte keeps its meaning (object id / draw register) */
 #define MG_MAX_VIEW 31    /* view_size (agents.py:19-35: any; a view row is a 32-bit mask here) */
 #define MG_KEY_WORDS 2
 #define MG_MT_N 624
@@ -218,7 +223,13 @@ typedef struct MgGenOp {
                                    * max_tries < 0: a DRAW, `self._rand_int(x0, x1)` inside `_gen_grid`: draw[obj] = x0 +
                                    * bounded(x1 - x0 - 1) on the env's RNG (numpy's randint: masked rejection; a one-value
                                    * range consumes nothing), obj in [0, MG_GEN_DRAWS); count, y0, y1 and reject are unused.
-                                   * The draws live for the duration of ONE reset; they are no part of MgState. */
+                                   * The draws live for the duration of ONE reset; they are no part of MgState; every
+                                   * register is 0 when a reset begins.
+                                   * `obj` is the object id (the draw register of a DRAW) in its LOW BYTE.  With MG_GEN_GUARD
+                                   * (bit 30) the op is GUARDED — a branch of `_gen_grid` on a draw, flattened: r = bits 24-26,
+                                   * hi = bits 16-23, lo = bits 8-15, and the op runs only in an env with lo <= draw[r] <= hi.
+                                   * A guard that is false skips the op entirely: no RNG word, no write, no error, and a guarded
+                                   * DRAW leaves its register as it was.  Without the bit the upper bits are zero. */
     int32_t x0, y0, x1, y1;       /* sampling rectangle [x0,x1) x [y0,y1): place_obj(top=, size=) clamped
                                    * to the grid (base.py:692-695); the whole grid by default.  Each of the four is a plain
                                    * integer or, with MG_GEN_SYM, `const +- draw[r]` of an EARLIER draw op — evaluated per env

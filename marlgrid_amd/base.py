@@ -60,7 +60,8 @@ def _on_device(fn):
 
 _NO_BRANCH = ("a value of self._rand_int(...) inside _gen_grid is drawn later, per env, on the device: _gen_grid may compute "
               "with it (draw + k, k + draw, draw - k, k - draw with Python ints) and hand the result to put_obj / grid.set / the "
-              "wall helpers / place_obj(top=, size=) / a later _rand_int, but it cannot branch on it (%s)")
+              "wall helpers / place_obj(top=, size=) / a later _rand_int, but it cannot branch on it (%s) — self._fork(draw) hands "
+              "its value over as a Python int, one recorded path per value; self._rand_elem(...) / self._rand_bool() draw and fork")
 
 
 class GenDraw(object):
@@ -122,6 +123,15 @@ def _gen_enc(v):
 
 def _any_draw(*vs):
     return any(isinstance(v, GenDraw) for v in vs)
+
+
+def _same_spawn(a, b):
+    """two `agent_spawn_kwargs` left by two runs of one `_gen_grid` (callables by identity)"""
+    a, b = a or {}, b or {}
+    if set(a) != set(b):
+        return False
+    return all(a[k] is b[k] if callable(a[k]) else (tuple(a[k]) == tuple(b[k]) if isinstance(a[k], (tuple, list)) else a[k] == b[k])
+               for k in a)
 
 
 class ObjectRegistry(object):
@@ -1034,6 +1044,8 @@ class MultiGridEnv(object):
         self._tr_ops = []
         self._tr_late = {}          # index into _tr_ops -> the symbolic form of a static edit recorded as op(s)
         self._tr_draws = []         # per `_rand_int` so far: the (lowest, highest) value it can take, over all earlier draws
+        self._tr_guard = 0          # the guard bits (MG_GEN_GUARD) of the branch being recorded: ORed into every op's `obj`
+        self._tr_fork_i = 0         # forks met so far in this run of `_gen_grid` (an index into _tr_path)
 
     def _tr_static(self, sym, key, rects):
         """A static layout edit of `_gen_grid` (grid.set / put_obj / the wall helpers).  Before the first random
@@ -1049,16 +1061,16 @@ class MultiGridEnv(object):
             # a fill that continues the one before it (same object, same rows or columns, adjacent) is the same op, larger
             last = self._tr_ops[-1]
             merged = None
-            if last[2] == 0 and last[0] == int(key) and last[7] is None and not any(v & N.GEN_SYM for v in last[3:7]):
+            if last[2] == 0 and last[0] == int(key) | self._tr_guard and last[7] is None and not any(v & N.GEN_SYM for v in last[3:7]):
                 lx0, ly0, lx1, ly1 = last[3:7]
                 if (ly0, ly1) == (y0, y1) and (lx1 == x0 or x1 == lx0):
-                    merged = (int(key), 1, 0, min(lx0, x0), y0, max(lx1, x1), y1, None)
+                    merged = (last[0], 1, 0, min(lx0, x0), y0, max(lx1, x1), y1, None)
                 elif (lx0, lx1) == (x0, x1) and (ly1 == y0 or y1 == ly0):
-                    merged = (int(key), 1, 0, x0, min(ly0, y0), x1, max(ly1, y1), None)
+                    merged = (last[0], 1, 0, x0, min(ly0, y0), x1, max(ly1, y1), None)
             if merged is not None:
                 self._tr_ops[-1] = merged
             else:
-                self._tr_ops.append((int(key), 1, 0, x0, y0, x1, y1, None))
+                self._tr_ops.append((int(key) | self._tr_guard, 1, 0, x0, y0, x1, y1, None))
             if first is None:
                 first = len(self._tr_ops) - 1
         if first is not None:
@@ -1098,9 +1110,82 @@ class MultiGridEnv(object):
                              % (low, high, vmin, vmax))
         reg = len(self._tr_draws)
         self._tr_draws.append((vmin, vmax))
-        self._tr_ops.append((reg, 1, -1, _gen_enc(low), 0, _gen_enc(high), 0, None))
+        self._tr_ops.append((reg | self._tr_guard, 1, -1, _gen_enc(low), 0, _gen_enc(high), 0, None))
         self._tr_late[len(self._tr_ops) - 1] = [("draw", reg, _gen_enc(low), _gen_enc(high))]
         return GenDraw(reg)
+
+    # ---- branching on a draw: one recorded run of `_gen_grid` per path, merged into one guarded program --------------
+    def _fork(self, d):
+        """The value of `d` — an int, or a `_rand_int` result (`const +- draw[r]`) — as a plain Python int: `_gen_grid` may
+        then do with it whatever Python does with an int (`if`, `range`, indexing, arithmetic).  The recorder runs
+        `_gen_grid` once per value the draw can take here (at most 16; depth first over the forks met so far, at most 64
+        paths) and merges the runs into one reset program: what was recorded before the fork once, then every branch's ops
+        under a guard `draw[r] == value` (MgGenOp.obj, MG_GEN_GUARD) that each env evaluates for itself on the device.
+        `_gen_grid` is therefore run SEVERAL TIMES and must be a function of its arguments and its draws alone."""
+        if isinstance(d, (int, np.integer)) and not isinstance(d, bool):
+            return int(d)
+        if not isinstance(d, GenDraw):
+            raise TypeError("_fork takes an int or a value of self._rand_int(...), not %s" % type(d).__name__)
+        if not self._tracing or self._tr_grid is None:
+            raise NotImplementedError(_NO_BRANCH % "_fork outside _gen_grid")
+        r = d.reg
+        lo, hi = self._tr_draws[r]
+        if lo == hi:                # decided on this path already (a one-value range, or forked before): nothing to guard
+            return d.const + d.sign * lo
+        if hi - lo + 1 > 16:
+            raise NotImplementedError("_gen_grid: a fork over more than 16 values (draw[%d] takes %d..%d here): every value is a "
+                                      "recorded path of its own" % (r, lo, hi))
+        i = self._tr_fork_i
+        self._tr_fork_i += 1
+        if i == len(self._tr_path):             # met for the first time: take its first value; the later ones are later runs
+            q = None
+            if self._tr_guard:
+                q = len(self._tr_draws)         # a branch inside a branch: the conjunction through a spare register
+                if q >= N.GEN_DRAWS:
+                    raise NotImplementedError("_gen_grid needs more than %d draw registers (MG_GEN_DRAWS) on one path: %d "
+                                              "_rand_int draws and the copies that forks inside a branch of another draw take"
+                                              % (N.GEN_DRAWS, N.GEN_DRAWS))
+                if hi + 1 > 255:
+                    raise NotImplementedError("_gen_grid: a fork inside a branch of another draw, on a draw that may be 255: its "
+                                              "copy `draw + 1` must fit a byte of the draw registers")
+            self._tr_path.append(dict(values=list(range(lo, hi + 1)), idx=0, q=q, zero=q in self._tr_written))
+        f = self._tr_path[i]
+        if f["values"] != list(range(lo, hi + 1)):
+            raise ValueError("_gen_grid is not a function of its arguments and its draws: run again for another path it forked "
+                             "over other values")
+        v = f["values"][f["idx"]]
+        self._tr_draws[r] = (v, v)              # inside the branch the draw's interval is the guard's: every later proof is per path
+        if f["q"] is None:
+            self._tr_guard = self._guard_bits(r, v, v)
+        else:
+            # under the outer guard: q = draw[r] + 1, a one-value DRAW (no RNG word).  Registers start every reset at 0 — a
+            # number that a branch recorded earlier may have written is zeroed first, in every env —, so q == v + 1 says
+            # "the outer branch was taken and draw[r] == v"
+            q = f["q"]
+            src = GenDraw(r)
+            if f["zero"]:
+                self._tr_ops.append((q, 1, -1, 0, 0, 1, 0, None))
+                self._tr_late[len(self._tr_ops) - 1] = [("draw", q, 0, 1)]
+            self._tr_ops.append((q | self._tr_guard, 1, -1, (src + 1).encode(), 0, (src + 2).encode(), 0, None))
+            self._tr_late[len(self._tr_ops) - 1] = [("draw", q, (src + 1).encode(), (src + 2).encode())]
+            self._tr_draws.append((v + 1, v + 1))
+            self._tr_guard = self._guard_bits(q, v + 1, v + 1)
+        f["start"] = len(self._tr_ops)          # the branch's own ops begin here
+        return d.const + d.sign * v
+
+    @staticmethod
+    def _guard_bits(r, lo, hi):
+        return N.GEN_GUARD | (r << N.GEN_GUARD_DRAW_SHIFT) | (hi << N.GEN_GUARD_HI_SHIFT) | (lo << N.GEN_GUARD_LO_SHIFT)
+
+    def _rand_elem(self, iterable):
+        """gym-minigrid's `_rand_elem`: one element of `iterable`, by a `_rand_int(0, len)` draw.  Inside `_gen_grid` the draw
+        is recorded and forked on (`_fork`): the element that comes back is the concrete one of the path being recorded."""
+        lst = list(iterable)
+        return lst[self._fork(self._rand_int(0, len(lst)))]
+
+    def _rand_bool(self):
+        """gym-minigrid's `_rand_bool`: `self.np_random.randint(0, 2) == 0` — a draw of (0, 2) and a fork on it"""
+        return self._fork(self._rand_int(0, 2)) == 0
 
     def _tr_fill_sym(self, key, rects):
         """A static edit with a draw among its coordinates: one fill op per rectangle, its operands evaluated per env on the
@@ -1112,7 +1197,7 @@ class MultiGridEnv(object):
                 raise ValueError("_gen_grid: the edit of cells [%r, %r) x [%r, %r) is not inside the %d x %d grid and non-empty for "
                                  "every value the draws can take" % (rect[0], rect[2], rect[1], rect[3], self.width, self.height))
             enc = tuple(_gen_enc(v) for v in rect)
-            self._tr_ops.append((int(key), 1, 0) + enc + (None,))
+            self._tr_ops.append((int(key) | self._tr_guard, 1, 0) + enc + (None,))
             self._tr_late[len(self._tr_ops) - 1] = [("fill", int(key)) + enc]
             # every cell the edit can reach may have been written: get() there warns
             g._maybe[min(c[0] for c in cases):max(c[2] for c in cases), min(c[1] for c in cases):max(c[3] for c in cases)] = True
@@ -1139,30 +1224,73 @@ class MultiGridEnv(object):
         return (x0, y0, x1, y1), hull
 
     def _trace_gen_grid(self):
-        self._tracing = True
-        self._tr_grid = None
-        _trace.env = self
-        try:
-            self._gen_grid(self.width, self.height)
-        finally:
-            _trace.env = None
-            self._tracing = False
-        g = self._tr_grid
-        if g is None or self.grid is not g:
-            raise RuntimeError("_gen_grid must assign self.grid = MultiGrid((width, height))")
-        kw = self.agent_spawn_kwargs or {}
-        if _any_draw(*[v for k in ("top", "size") if kw.get(k) is not None for v in kw[k]]):
-            raise NotImplementedError("agent_spawn_kwargs with a _rand_int draw: the spawn rectangle is also used by respawn and "
-                                      "late spawns, long after the reset that made the draw — not supported")
-        if len(self._tr_ops) > N.MAX_GEN:
-            fills = sum(1 for op in self._tr_ops if op[2] == 0)
+        """Record `_gen_grid`: once if it forks on no draw, else once per path (`_fork`), depth first, every run from a fresh
+        MultiGrid and recorder state; the runs merged into ONE program — the ops before a fork once, then each branch's ops
+        under its guard, recursively (a path's ops are contiguous from its last fork on: no branch rejoins)."""
+        self._tr_path = []          # the forks of the path being recorded: dict(values, idx, q, zero, start)
+        self._tr_written = set()    # draw registers that the branches recorded so far write
+        merged = sym = late = template = grid = spawn = None
+        runs = 0
+        while True:
+            runs += 1
+            if runs > 64:
+                raise NotImplementedError("_gen_grid forks into more than 64 paths: every path is recorded by a run of its own and "
+                                          "every env replays the whole merged program")
+            self._tracing = True
+            self._tr_grid = None
+            _trace.env = self
+            try:
+                self._gen_grid(self.width, self.height)
+            finally:
+                _trace.env = None
+                self._tracing = False
+            g = self._tr_grid
+            if g is None or self.grid is not g:
+                raise RuntimeError("_gen_grid must assign self.grid = MultiGrid((width, height))")
+            kw = self.agent_spawn_kwargs or {}
+            if _any_draw(*[v for k in ("top", "size") if kw.get(k) is not None for v in kw[k]]):
+                raise NotImplementedError("agent_spawn_kwargs with a _rand_int draw: the spawn rectangle is also used by respawn and "
+                                          "late spawns, long after the reset that made the draw — not supported")
+            if self._tr_fork_i != len(self._tr_path):
+                raise ValueError("_gen_grid is not a function of its arguments and its draws: run again for another path it made "
+                                 "fewer forks")
+            if merged is None:
+                merged, sym, late, template = list(self._tr_ops), list(self._tr_sym), dict(self._tr_late), g._template
+                grid, spawn = g, self.agent_spawn_kwargs
+            else:
+                # the run shares everything before the fork whose next value it took with the runs before it
+                if (self._tr_ops[:shared] != prefix or self._tr_sym != sym or not np.array_equal(g._template, template)):
+                    raise ValueError("_gen_grid is not a function of its arguments and its draws: run again for another path it "
+                                     "recorded another layout before the fork")
+                if not _same_spawn(self.agent_spawn_kwargs, spawn):
+                    raise ValueError("_gen_grid leaves agent_spawn_kwargs that differ between the paths of a fork: the spawn "
+                                     "rectangle is the launch's, not an env's")
+                for i, e in self._tr_late.items():
+                    if i >= shared:
+                        late[len(merged) + i - shared] = e
+                merged.extend(self._tr_ops[shared:])
+                # the grid that stays is the first run's: a cell that another path draws differently, or may have filled,
+                # counts as "may have been written" there (`grid.get()` warns on it, whatever path is asked about)
+                grid._maybe |= g._maybe | (g._shadow != grid._shadow)
+            self._tr_written.update(op[0] & (N.GEN_DRAWS - 1) for op in self._tr_ops if op[2] < 0)
+            while self._tr_path and self._tr_path[-1]["idx"] + 1 == len(self._tr_path[-1]["values"]):
+                self._tr_path.pop()
+            if not self._tr_path:
+                break
+            self._tr_path[-1]["idx"] += 1       # the next path: the deepest fork with a value left takes it
+            shared = self._tr_path[-1]["start"]
+            prefix = self._tr_ops[:shared]
+        self.grid = self._tr_grid = grid        # (the first run's: the template is the same in every run, `_maybe` covers them all)
+        if len(merged) > N.MAX_GEN:
+            fills = sum(1 for op in merged if op[2] == 0)
             raise NotImplementedError("_gen_grid records %d reset-program ops — %d groups of random placements and %d rectangle "
                                       "fills for static edits made after the first place_obj — and a device program holds at most "
                                       "%d (MG_MAX_GEN: a sanity bound — every env replays the whole program at every reset): draw the "
                                       "static layout before the first place_obj (it then costs nothing)"
-                                      % (len(self._tr_ops), len(self._tr_ops) - fills, fills, N.MAX_GEN))
-        self._spec_last = dict(sym=list(self._tr_sym), ops=list(self._tr_ops), late=dict(self._tr_late))
-        return g._template, list(self._tr_ops)
+                                      % (len(merged), len(merged) - fills, fills, N.MAX_GEN))
+        self._tr_ops, self._tr_late = merged, late
+        self._spec_last = dict(sym=list(sym), ops=list(merged), late=dict(late))
+        return template, list(merged)
 
     @_on_device
     def put_obj(self, obj, i, j, env_mask=None):
@@ -1252,6 +1380,7 @@ class MultiGridEnv(object):
         else:
             operands = region = self._place_region(top, size)
         rej = self._reject_table(reject_fn, region)
+        key |= self._tr_guard
         op = (key, 1, max_tries) + operands + (None if rej is None else rej.tobytes(),)
         x0, y0, x1, y1 = region
         may = self._tr_grid._shadow[x0:x1, y0:y1] == 0          # (only empty cells accept a placement, base.py:672-679)
@@ -1515,10 +1644,14 @@ class MultiGridEnv(object):
         host_ops = (N.GenOp * max(1, len(ops)))()
         for i, (obj, count, max_tries, x0, y0, x1, y1, rej) in enumerate(ops):
             # (the library cannot look into device memory from the host: what the kernels rely on is checked here)
+            # the guard of a branch in the upper bits of obj (MG_GEN_GUARD): lo <= hi; the low byte as ever
+            guard, low = obj & ~0xFF, obj & 0xFF
+            assert guard == 0 or (guard & ~0x07FFFF00 == N.GEN_GUARD
+                                  and (guard >> N.GEN_GUARD_LO_SHIFT) & 0xFF <= (guard >> N.GEN_GUARD_HI_SHIFT) & 0xFF)
             if max_tries < 0:       # a `_rand_int` draw: obj is its register
-                assert 0 <= obj < N.GEN_DRAWS
+                assert 0 <= low < N.GEN_DRAWS
             else:
-                assert (1 if max_tries > 0 else 0) <= obj < len(self.obj_reg.objs) and count >= 0
+                assert (1 if max_tries > 0 else 0) <= low < len(self.obj_reg.objs) and count >= 0
                 # (a rectangle with a draw operand was proved by the recorder and is clamped on the device)
                 assert any(v & N.GEN_SYM for v in (x0, y0, x1, y1)) or (0 <= x0 < x1 <= self.width and 0 <= y0 < y1 <= self.height)
             o = host_ops[i]
@@ -2055,6 +2188,20 @@ class MultiGridEnv(object):
             out = list(p["sym"])
             late = p.get("late", {})
             for i, (k, c, t, x0, y0, x1, y1, rej) in enumerate(p["ops"]):
+                if k & N.GEN_GUARD and k & ~0xFF:
+                    # an op of a branch on a draw: ("guard", r, lo, hi, entry) — the entry as below, run only where
+                    # lo <= draw[r] <= hi (no oracle replays these)
+                    grd = ("guard", (k >> N.GEN_GUARD_DRAW_SHIFT) & 7, (k >> N.GEN_GUARD_LO_SHIFT) & 0xFF,
+                           (k >> N.GEN_GUARD_HI_SHIFT) & 0xFF)
+                    if t <= 0:
+                        out.extend(grd + (e,) for e in late.get(i, []))
+                    else:
+                        entry = ("place_sym", k & 0xFF, c, t, x0, y0, x1, y1)
+                        if rej is not None:
+                            cells = np.argwhere(np.frombuffer(rej, np.uint8).reshape(self.width, self.height))
+                            entry += (tuple((int(x), int(y)) for x, y in cells),)
+                        out.append(grd + (entry,))
+                    continue
                 if t <= 0:               # a static edit after a placement, or a draw: its symbolic form, once
                     out.extend(late.get(i, []))
                     continue

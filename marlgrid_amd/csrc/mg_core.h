@@ -466,6 +466,15 @@ MG_HD int gen_operand(int32_t v, uint64_t draws) {
     const int c = sym ? (int)(int16_t)(v & 0xFFFF) : v;
     return (v & MG_GEN_NEG) ? c - d : c + d;
 }
+// the guard of a reset-program op (marlgrid_hip.h MG_GEN_GUARD, the upper bits of MgGenOp.obj): true = the op is skipped —
+// guarded, and draw[r] outside lo..hi.  One unsigned compare: (d - lo) <= (hi - lo); an unguarded op has bit 30 clear
+MG_HD bool gen_skipped(int32_t obj, uint64_t draws) {
+    const int r = (obj >> MG_GEN_GUARD_DRAW_SHIFT) & (MG_GEN_DRAWS - 1);
+    const uint32_t half = (r & 4) ? (uint32_t)(draws >> 32) : (uint32_t)draws;
+    const uint32_t d = (half >> ((r & 3) * 8)) & 0xFFu;
+    const uint32_t lo = ((uint32_t)obj >> MG_GEN_GUARD_LO_SHIFT) & 0xFFu, hi = ((uint32_t)obj >> MG_GEN_GUARD_HI_SHIFT) & 0xFFu;
+    return (obj & MG_GEN_GUARD) != 0 && d - lo > hi - lo;
+}
 // One register that the compiler keeps as ONE register: a value packed for the length of a loop is not taken apart ahead of
 // the loop again (reset_env's sampling rectangle: four registers per lane across every RNG refill otherwise)
 MG_HD uint32_t keep_packed(uint32_t v) {
@@ -496,6 +505,8 @@ MG_HD int reset_env(const MgConfig& cfg, const MgState& st, const MgGenProgram& 
     uint64_t draws = 0;
     for (int o = 0; o < prog.n_ops && !err; o++) {
         MgGenOp op = prog.ops[o];
+        // a branch of `_gen_grid` this env's draws did not take: no RNG word, no write, no error, a draw register as it was
+        if (gen_skipped(op.obj, draws)) continue;
         // operands `const +- draw[r]` (branch-free: a plain operand evaluates to itself); a fill or place rectangle with one is
         // clamped to the grid — place_obj's own clamp, base.py:692-695; for a fill: whatever program a caller hands over,
         // nothing is written outside the env's grid slice

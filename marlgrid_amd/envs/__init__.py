@@ -7,16 +7,19 @@ stands in for `gym.make`.
 defines the method, doorkey.py:26,34).  Its `_gen_grid` lays the room out from random draws — `MultiGridEnv._rand_int`
 inside `_gen_grid` is recorded and drawn per env on the device at every reset.  A recorded `_gen_grid` may compute with a
 draw (`draw +- int`) and use it as a coordinate or extent of put_obj / grid.set / the wall helpers, in place_obj's `top` /
-`size` and as a bound of a later `_rand_int`; it still cannot BRANCH on one (compare it, index or loop with it), choose an
-object by it, put it into `agent_spawn_kwargs`, or have a `reject_fn` that depends on it.  Upstream registers no DoorKey
-id; the ids in `extension_envs` are this package's own and are built by `make` like the registered ones.
+`size` and as a bound of a later `_rand_int`.  To BRANCH on one (compare it, index or loop with it, choose an object by
+it) `_gen_grid` asks for its value with `self._fork(draw)`, or draws with `self._rand_elem(...)` / `self._rand_bool()`: it is
+then recorded once per path and every env runs the ops of its own path (`ColoredDoorKeyEnv`: a door and key of one of six
+colours).  It still cannot put a draw into `agent_spawn_kwargs` or have a `reject_fn` that depends on one.  Upstream registers
+no DoorKey id; the ids in `extension_envs` are this package's own and are built by `make` like the registered ones.
 """
 import functools
 import random
 
 from ..agents import GridAgentInterface
 from ..base import MultiGridEnv
-from .scenarios import ClutteredGoalCycleEnv, ClutteredMultiGrid, DoorKeyEnv, EmptyMultiGrid, VisibilityTestEnv
+from .scenarios import (ClutteredGoalCycleEnv, ClutteredMultiGrid, ColoredDoorKeyEnv, DoorKeyEnv, EmptyMultiGrid,  # noqa: F401
+                        VisibilityTestEnv)
 
 _PALETTE = ("red", "blue", "purple", "orange", "olive", "pink")     # per-slot agent colours of a registered id
 _registry = {}            # id -> factory(**constructor kwargs)
@@ -119,4 +122,6 @@ for _row in (
                       env_kwargs=_row[6])
 for _row in (("MarlGrid-2AgentDoorKey6x6-v0", 6), ("MarlGrid-2AgentDoorKey8x8-v0", 8)):
     register_marl_env(_row[0], DoorKeyEnv, n_agents=2, grid_size=_row[1], view_size=7, listed_in=extension_envs)
+register_marl_env("MarlGrid-2AgentColoredDoorKey8x8-v0", ColoredDoorKeyEnv, n_agents=2, grid_size=8, view_size=7,
+                  listed_in=extension_envs)
 del _row

@@ -132,6 +132,20 @@ class DoorKeyEnv(_WalledRoom):
         split = self._rand_int(2, width - 2)                 # the splitting wall
         self.grid.vert_wall(split, 0)
         door = self._rand_int(1, width - 2)                  # (upstream draws the row from the WIDTH)
-        self.put_obj(Door(color="yellow", state=Door.states.locked), split, door)
-        self.place_obj(obj=Key("yellow"), top=(0, 0), size=(split, height))
+        color = self._door_color()
+        self.put_obj(Door(color=color, state=Door.states.locked), split, door)
+        self.place_obj(obj=Key(color), top=(0, 0), size=(split, height))
         self._spawn_anywhere()
+
+    def _door_color(self):
+        return "yellow"
+
+
+class ColoredDoorKeyEnv(DoorKeyEnv):
+    """`DoorKeyEnv` whose door and key share one colour out of six, drawn per env at every reset after the split column and
+    the door row: `_rand_elem` records the draw and forks on it, so the door and the key are placed by six guarded pairs of
+    ops of which every env runs one."""
+    door_colors = ("red", "green", "blue", "purple", "yellow", "grey")      # gym-minigrid's six, all of objects.COLORS
+
+    def _door_color(self):
+        return self._rand_elem(self.door_colors)

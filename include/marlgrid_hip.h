@@ -307,7 +307,8 @@ int32_t mg_step_render_encode(const MgConfig* cfg, const MgState* st, const void
  * flags: MG_DELTA_FORCE — every band counts as changed and the signature is only recorded: the first call for a pair
  * (obs, signature), and every call after anything else wrote into `obs` (mg_render_obs, the caller itself) or the atlas or the
  * object table behind cfg changed — or, in stream order and therefore also for launches replayed from a captured graph, a
- * signature filled with 0xFF bytes (the entry 0xFFFF is no tile: every band compares unequal).  The bytes in `obs` after the
+ * signature filled with 0xFF bytes (a 0xFF fill is no tile in either layout the library keeps there — 16-bit entries, or one-byte
+ * codes where the configuration's tiles fit a byte —: every band compares unequal).  The bytes in `obs` after the
  * call are mg_step_render's.
  * MG_E_UNSUPPORTED — nothing launched, call mg_step_render — unless: view 7 with 8-pixel tiles, at most 3 agents, no 'prestige'
  * agent, grid and atlas in LDS. */

@@ -183,7 +183,8 @@ static mg::FusedStep fused_step_of(const MgConfig* cfg, const void* actions, int
     fs.has_ep = ep ? 1 : 0;
     if (ep) fs.ep = *ep;
     fs.sig = sig;
-    fs.sig_force = (sig_flags & MG_DELTA_FORCE) ? 1 : 0;
+    fs.sig_flags = ((sig_flags & MG_DELTA_FORCE) ? mg::kSigForce : 0) |
+                   (mg::delta_sig_compact(cfg->n_tiles, cfg->n_agents, cfg->view_size) ? 0 : mg::kSigWide);
     return fs;
 }
 

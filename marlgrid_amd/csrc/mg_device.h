@@ -66,9 +66,13 @@ struct FusedStep {
                               //     4 k + dir —, (n_obj + 4 n) rounded up to 16 (mg_render_pick.h: render_enc_entries; 0: none)
     int32_t has_ep;           // mg_step_render_ep: `ep` is set — the launcher then takes an instantiation with the episode code
     MgEpisode ep;             //     compiled in (V + 32); the plain ones never look at either
-    uint16_t* sig;            // mg_step_render_delta (V + 64): per env the tmap — RenderScratch::tmap_stride bytes — of what `obs` holds
-    int32_t sig_force;        //     for it (null: not asked for); sig_force: every band counts as changed, the signature is only recorded
+    uint16_t* sig;            // mg_step_render_delta (V + 64): the signature of what `obs` holds (null: not asked for) — compact: per agent
+                              //     image a 64-byte slot of one-byte codes, env e at e * n * 64 (delta_sig_*, mg_step_layout.h); kSigWide:
+                              //     per env the tmap's 16-bit entries, RenderScratch::tmap_stride bytes
+    int32_t sig_flags;        //     kSigForce — every band counts as changed, the signature is only recorded — | kSigWide — the 16-bit
+                              //     layout, for a configuration whose codes do not fit a byte (the launcher: delta_sig_compact)
 };
+enum { kSigForce = 1, kSigWide = 2 };
 
 // x / d for small operands (x * d < 2^32) by multiply-high with ceil(2^32 / d): item index -> (slot, rest)
 struct SmallDiv {

@@ -534,8 +534,11 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
             constexpr int kSigQ = 3;                                        // render_delta_fits: a batch's signatures are <= 3 KiB
             if constexpr (kDelta) {
                 const FusedStep& fsd = kernarg_again<FusedStep>(offsetof(RenderKernargs, fs));
-                const uint4* ssrc = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(fsd.sig) + (size_t)eb * L.tmap_stride);
-                const int ns = fsd.sig_force ? 0 : kb * (L.tmap_stride / 16);
+                // (compact — delta_sig_compact, mg_step_layout.h —: a 64-byte slot of codes per agent image, env e at e * n * 64;
+                // else the 16-bit entries, a tmap slot per env)
+                const int sig_env = (fsd.sig_flags & kSigWide) ? L.tmap_stride : n * kDeltaSigSlot;
+                const uint4* ssrc = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(fsd.sig) + (size_t)eb * sig_env);
+                const int ns = (fsd.sig_flags & kSigForce) ? 0 : kb * (sig_env / 16);
                 typedef const __attribute__((address_space(1))) void* gptr;
                 typedef __attribute__((address_space(3))) void* lptr;
 #pragma unroll
@@ -1123,16 +1126,44 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
                 uint16_t* row = w_tmap + __umul24(g, (uint32_t)(L.tmap_stride / 2)) + __umul24(r, (uint32_t)VS);
                 if constexpr (kDelta) {
                     // the band's final tiles against the recorded ones (exact: the entry — tile, orientation, overlay — is the pixels)
-                    // (an entry is a multiple of the tile's dwords and below the atlas's size: 0xFFFF is none — a signature a host
-                    // has filled with 0xFF, in stream order, makes every band count as changed)
-                    const uint16_t* orow = w_tmap0 + __umul24((uint32_t)ej + g, (uint32_t)(L.tmap_stride / 2)) + __umul24(r, (uint32_t)VS);
-                    uint32_t diff = (uint32_t)kernarg_again<FusedStep>(offsetof(RenderKernargs, fs)).sig_force;
+                    // (a 0xFF fill is no tile in either layout: a 16-bit entry is a multiple of the tile's dwords and below the atlas's
+                    // size, so 0xFFFF is none; a compact code is below 0xFF — a signature a host has filled with 0xFF, in stream
+                    // order, makes every band count as changed)
+                    const uint32_t sigf = (uint32_t)kernarg_again<FusedStep>(offsetof(RenderKernargs, fs)).sig_flags;
+                    uint32_t diff = sigf & kSigForce;
+                    if (sigf & kSigWide) {
+                        const uint16_t* orow = w_tmap0 + __umul24((uint32_t)ej + g, (uint32_t)(L.tmap_stride / 2)) + __umul24(r, (uint32_t)VS);
 #pragma unroll
-                    for (int va = 0; va < VS_; va++) {
-                        const bool vis = (mask >> va) & 1u;
-                        const uint32_t nw = vis ? (uint32_t)row[va] : 0u;
-                        diff |= nw ^ (uint32_t)orow[va];
-                        if (!vis) row[va] = 0;
+                        for (int va = 0; va < VS_; va++) {
+                            const bool vis = (mask >> va) & 1u;
+                            const uint32_t nw = vis ? (uint32_t)row[va] : 0u;
+                            diff |= nw ^ (uint32_t)orow[va];
+                            if (!vis) row[va] = 0;
+                        }
+                    } else {
+                        // the compact signature: the band's VS codes in the image's 64-byte slot (image (ej + g) * n + v of the
+                        // staged batch; r = v * VS + view row, so the band begins at byte 7 r + 15 v of the env's slots), compared
+                        // as the entries they stand for — 0xFF stands for none — and replaced IN PLACE by the band's new codes:
+                        // the env's slots then hold its new signature, which goes back from there.  (All reads before the writes:
+                        // a byte pointer may alias anything, one by one they would be seven dependent round trips.)
+                        constexpr uint32_t kTileDw = TS_ * TS_ * 3 / 4;
+                        const uint32_t v = by_VS.template div<true>(r);
+                        uint8_t* orow = reinterpret_cast<uint8_t*>(w_tmap0) + __umul24(__umul24((uint32_t)ej + g, (uint32_t)n) + v, (uint32_t)kDeltaSigSlot) +
+                                        __umul24(r - __umul24(v, (uint32_t)VS), (uint32_t)VS);
+                        uint32_t nw[VS_ ? VS_ : 1], oc[VS_ ? VS_ : 1];
+#pragma unroll
+                        for (int va = 0; va < VS_; va++) { nw[va] = (uint32_t)row[va]; oc[va] = (uint32_t)orow[va]; }
+#pragma unroll
+                        for (int va = 0; va < VS_; va++) {
+                            const bool vis = (mask >> va) & 1u;
+                            if (!vis) nw[va] = 0u;
+                            diff |= nw[va] ^ delta_sig_entry(oc[va], kTileDw);
+                        }
+#pragma unroll
+                        for (int va = 0; va < VS_; va++) {
+                            if (!((mask >> va) & 1u)) row[va] = 0;
+                            orow[va] = (uint8_t)delta_sig_code(nw[va], kTileDw);
+                        }
                     }
                     if (diff) atomicOr(&w_chg[g], 1u << r);
                 } else
@@ -1150,8 +1181,23 @@ __global__ __launch_bounds__(WPB * 64) void render_kernel(MgConfig cfg, MgState 
         }
         wave_lds_sync();
         if constexpr (kDelta) {        // the group's new signatures, as the run of 16-byte pieces they are (the padding of a slot: whatever is there)
-            uint4* sdst = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(kernarg_again<FusedStep>(offsetof(RenderKernargs, fs)).sig) + (size_t)e * L.tmap_stride);
-            for (int i = lane; i < G * (L.tmap_stride / 16); i += kWave) sdst[i] = reinterpret_cast<const uint4*>(w_tmap_g)[i];
+            const FusedStep& fsd = kernarg_again<FusedStep>(offsetof(RenderKernargs, fs));
+            if (fsd.sig_flags & kSigWide) {
+                uint4* sdst = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(fsd.sig) + (size_t)e * L.tmap_stride);
+                for (int i = lane; i < G * (L.tmap_stride / 16); i += kWave) sdst[i] = reinterpret_cast<const uint4*>(w_tmap_g)[i];
+            } else {
+                // compact: the slots of the images with a changed band, whole — an image without one has, by definition, the
+                // signature it had (forced, or after an invalidation, every band counts as changed: everything is written)
+                const uint32_t env_b = (uint32_t)(n * kDeltaSigSlot);
+                uint4* sdst = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(fsd.sig) + (size_t)e * env_b);
+                const uint4* ssrc = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(w_tmap0) + __umul24((uint32_t)ej, env_b));
+                int lane_s = lane;
+                asm volatile("" : "+v"(lane_s));
+                for (int i = lane_s; i < G * n * (kDeltaSigSlot / 16); i += kWave) {
+                    const uint32_t img = (uint32_t)i / (kDeltaSigSlot / 16), g = by_n.div(img), v = img - __umul24(g, (uint32_t)n);
+                    if ((w_chg[g] >> __umul24(v, (uint32_t)VS)) & ((1u << VS) - 1u)) sdst[i] = ssrc[i];
+                }
+            }
         }
         } else {
         if constexpr (kPrestige) {

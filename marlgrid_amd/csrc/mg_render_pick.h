@@ -242,7 +242,8 @@ inline int render_min_lds_bytes(const MgConfig& cfg) {
 inline int choose_wpb(const MgConfig& cfg, int mode) { return cfg.B >= 4096 && render_fits(cfg, 16, mode) ? 16 : 4; }
 
 // mg_step_render_delta (V + 64), what its instantiations take from a wave's scratch WITHOUT growing it: the old signatures of a
-// staged batch land in the envs' own tmap slots with the staging loads (three 16-byte requests per lane: 3 KiB at most); the tmaps
+// staged batch land in the envs' own tmap slots with the staging loads (16-bit entries: a tmap slot per env, three 16-byte requests
+// per lane, 3 KiB at most; the compact codes of mg_step_layout.h — 64 bytes per agent image — take the front of the same area); the tmaps
 // of the view group being derived — two envs at 8-pixel tiles — and the group's two band-mask words live in the fused step's
 // columns (free once the batch is stepped); a band mask is one word (nv * vs bands).  At most three agents — whatever the grid
 // leaves of the batch size — is what all of it holds for.

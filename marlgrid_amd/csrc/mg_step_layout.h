@@ -80,4 +80,24 @@ MG_LAYOUT_FN int delta_wave_prio(int groups_done, int groups_total) {
     return 3 - q;
 }
 
+// mg_step_render_delta: the COMPACT signature.  A tmap entry of the delta instantiations is the tile's dword offset in the
+// atlas — (orientation * n_tiles + tile) * tile_dwords —, so the 16 bits of an entry say what the quotient says: its CODE,
+// one byte per view cell where the 4 * n_tiles codes leave 0xFF free (a host's 0xFF fill is then "no tile" in every cell).
+// Layout inside the allocation of MG_DELTA_SIG_BYTES per env, which stays: every agent image has a slot of
+// kDeltaSigSlot bytes of its own — vs * vs codes, [view row][view column], the rest padding —, env e begins at
+// e * n * kDeltaSigSlot and the tail of the allocation is unused.  Whole slots are what a launch reads (16 bytes a lane) and
+// what it writes back, and it writes back only the images with a changed band.  A configuration with more codes than a
+// byte holds keeps the 16-bit entries, MG_DELTA_SIG_BYTES per env, all of it rewritten by every launch.
+constexpr int kDeltaSigSlot = 64;
+constexpr uint32_t kDeltaSigNone = 0xFFu;
+MG_LAYOUT_FN bool delta_sig_compact(int n_tiles, int n_agents, int view_size) {
+    return 4 * n_tiles <= (int)kDeltaSigNone && view_size * view_size <= kDeltaSigSlot &&
+           n_agents * kDeltaSigSlot <= MG_DELTA_SIG_BYTES(n_agents, view_size);
+}
+MG_LAYOUT_FN uint32_t delta_sig_code(uint32_t entry, uint32_t tile_dwords) { return entry / tile_dwords; }
+MG_LAYOUT_FN uint32_t delta_sig_entry(uint32_t code, uint32_t tile_dwords) { return code * tile_dwords; }
+MG_LAYOUT_FN size_t delta_sig_env_bytes(int n_agents) { return (size_t)n_agents * kDeltaSigSlot; }
+// byte offset of the slot of env e's agent image v
+MG_LAYOUT_FN size_t delta_sig_slot(size_t e, int v, int n_agents) { return (e * (size_t)n_agents + (size_t)v) * kDeltaSigSlot; }
+
 }  // namespace mg

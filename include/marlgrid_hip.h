@@ -79,6 +79,7 @@ extern "C" {
 #define MG_GEN_SYM 0x40000000     /* an operand x0/y0/x1/y1 with this bit is `const +- draw[r]`, not a plain integer: */
 #define MG_GEN_NEG 0x20000000     /*   set: const - draw[r]; clear: const + draw[r] */
 #define MG_GEN_DRAW_SHIFT 16      /*   r = (operand >> 16) & 7; const = (int16_t)(operand & 0xFFFF) */
+#define MG_GEN_PARAM (-2)         /* MgGenOp.max_tries of a PARAM op: a draw register loaded from the env's row of the parameter table */
 /* the guard of a reset-program op, in the upper bits of MgGenOp.obj (values that were illegal before: ABI 6 still) */
 #define MG_GEN_GUARD 0x40000000   /* the op runs only if lo <= draw[r] <= hi (lo <= hi); else it is skipped entirely */
 #define MG_GEN_GUARD_DRAW_SHIFT 24 /*   r = (obj >> 24) & 7 */
@@ -225,6 +226,16 @@ typedef struct MgGenOp {
                                    * range consumes nothing), obj in [0, MG_GEN_DRAWS); count, y0, y1 and reject are unused.
                                    * The draws live for the duration of ONE reset; they are no part of MgState; every
                                    * register is 0 when a reset begins.
+                                   * max_tries == MG_GEN_PARAM (-2; a value that was meaningless before: ABI 6 still): a PARAM,
+                                   * `self._param(name, x0, x1)` inside `_gen_grid`: draw[obj] = clamp(params[env][y0], x0, x1 - 1)
+                                   * — a register loaded from the env's row of the parameter table (MgGenProgram.template_grid)
+                                   * instead of the RNG; no RNG word.  y0 in [0, MG_GEN_DRAWS) is the table column, [x0, x1) the
+                                   * declared interval (within 0..255).  The clamp makes a table of any bytes safe: no value moves
+                                   * a fill or a sampling rectangle outside what was proved for the interval.  Guardable like any
+                                   * op.  max_tries == -1 is the RNG draw.
+                                   * `count` of a placement may carry MG_GEN_SYM too (`const +- draw[r]`, illegal before): evaluated
+                                   * per env like the rectangle's operands, below 0 counts as 0; that many consecutive place_obj
+                                   * calls, consuming the same RNG words in the same order.
                                    * `obj` is the object id (the draw register of a DRAW) in its LOW BYTE.  With MG_GEN_GUARD
                                    * (bit 30) the op is GUARDED — a branch of `_gen_grid` on a draw, flattened: r = bits 24-26,
                                    * hi = bits 16-23, lo = bits 8-15, and the op runs only in an env with lo <= draw[r] <= hi.
@@ -242,7 +253,11 @@ typedef struct MgGenOp {
                                    * cannot run on the device; a function of the position alone is a table. */
 } MgGenOp;
 typedef struct MgGenProgram {
-    const uint8_t* template_grid; /* device, [cells_stride] */
+    const uint8_t* template_grid; /* device, [cells_stride].  A program that holds a PARAM op (MG_GEN_PARAM) is followed DIRECTLY by
+                                   * the parameter table: uint8_t params[B][MG_GEN_DRAWS] at template_grid + cells_stride, row = env,
+                                   * column = the op's y0; read at every reset of an env (a change takes effect at the env's next
+                                   * reset).  Every other program is the bytes it was and needs no tail.  (Not behind `ops`: the fused
+                                   * kernel reads programs of at most 32 ops from an LDS copy; template_grid is read in place.) */
     int32_t n_ops;
     const MgGenOp* ops;           /* DEVICE, [n_ops]: placements and late static edits, in `_gen_grid` order — upstream's `_gen_grid`
                                    * is free Python of any length (marlgrid/envs); the program lives in device memory, not in the

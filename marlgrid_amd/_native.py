@@ -11,6 +11,7 @@ MAX_AGENTS, MAX_OBJ, MAX_GEN, MAX_VIEW, KEY_WORDS, MT_N, MT_HEAD = 32, 256, 1024
 ABI_VERSION = 6
 # `_rand_int` draws of a reset program (MG_GEN_* in the C header): an operand with GEN_SYM is `const +- draw[r]`
 GEN_DRAWS, GEN_SYM, GEN_NEG, GEN_DRAW_SHIFT = 8, 0x40000000, 0x20000000, 16
+GEN_PARAM = -2              # GenOp.max_tries of a PARAM op (MG_GEN_PARAM): draw[obj] = clamp(params[env][y0], x0, x1 - 1), no RNG word
 # ... and the guard of an op, in the upper bits of GenOp.obj (MG_GEN_GUARD*): the op runs only where lo <= draw[r] <= hi
 GEN_GUARD, GEN_GUARD_DRAW_SHIFT, GEN_GUARD_HI_SHIFT, GEN_GUARD_LO_SHIFT = 0x40000000, 24, 16, 8
 

@@ -636,6 +636,10 @@ class MultiGridEnv(object):
         self._settings_seen = None
         self._tracing = False
         self._prog_cache = {}
+        self._param_decl = {}       # `_param` names of this env's `_gen_grid`: name -> dict(col, lo, hi, default); columns stay
+        self._param_buf = None      # the template of a program with a PARAM op and, behind it, the table (marlgrid_hip.h)
+        self._param_tpl = None      # ... the template bytes the buffer holds now
+        self.params_t = None        # the table: (B, MG_GEN_DRAWS) uint8 — a view of the buffer's tail (a numpy array when _dry)
         self._spec_ctor = None
         self._spec_last = None
         self._probe = None
@@ -1046,6 +1050,7 @@ class MultiGridEnv(object):
         self._tr_draws = []         # per `_rand_int` so far: the (lowest, highest) value it can take, over all earlier draws
         self._tr_guard = 0          # the guard bits (MG_GEN_GUARD) of the branch being recorded: ORed into every op's `obj`
         self._tr_fork_i = 0         # forks met so far in this run of `_gen_grid` (an index into _tr_path)
+        self._tr_params = {}        # `_param` names of this run: name -> (register, low, high)
 
     def _tr_static(self, sym, key, rects):
         """A static layout edit of `_gen_grid` (grid.set / put_obj / the wall helpers).  Before the first random
@@ -1113,6 +1118,151 @@ class MultiGridEnv(object):
         self._tr_ops.append((reg | self._tr_guard, 1, -1, _gen_enc(low), 0, _gen_enc(high), 0, None))
         self._tr_late[len(self._tr_ops) - 1] = [("draw", reg, _gen_enc(low), _gen_enc(high))]
         return GenDraw(reg)
+
+    # ---- per-env parameters: a register whose value comes from device memory, not from the RNG ----------------------
+    def _param(self, name, low, high, default=None):
+        """A per-env PARAMETER of the layout: inside `_gen_grid` this returns what `_rand_int(low, high)` returns — a
+        `GenDraw` over [low, high), within 0..255, usable wherever a draw is (`+- int`, coordinates and extents, place_obj's
+        `top` / `size` / `count`, bounds of a later `_rand_int`, `_fork`) — but every env reads its value from its row of a
+        byte table on the device (`env.params[name]`, `set_params`) when it resets, and no RNG word is consumed.  The
+        recorder's proofs run over the whole interval and the device clamps what it loads to it.  One draw register and
+        one table column per distinct name; naming a parameter again in the same `_gen_grid` returns the same register."""
+        if not self._tracing or self._tr_grid is None:
+            raise NotImplementedError(_NO_BRANCH % "_param outside _gen_grid, or before self.grid = MultiGrid(...)")
+        low, high = GenDraw._int(low, "_param(low=%s)" % type(low).__name__), GenDraw._int(high, "_param(high=%s)" % type(high).__name__)
+        if not 0 <= low < high <= 256:
+            raise ValueError("_param(%r, %d, %d): the interval [low, high) must be non-empty and within 0..255" % (name, low, high))
+        default = low if default is None else GenDraw._int(default, "_param(default=%s)" % type(default).__name__)
+        if not low <= default < high:
+            raise ValueError("_param(%r, %d, %d, default=%d): the default lies outside the interval" % (name, low, high, default))
+        seen = self._tr_params.get(name)
+        if seen is not None:
+            if seen[1:] != (low, high):
+                raise ValueError("_param(%r, %d, %d): declared as [%d, %d) earlier in this _gen_grid" % ((name, low, high) + seen[1:]))
+            return GenDraw(seen[0])
+        if len(self._tr_draws) >= N.GEN_DRAWS:
+            raise NotImplementedError("_gen_grid needs more than %d draw registers (MG_GEN_DRAWS): parameters share them with the "
+                                      "_rand_int draws and the copies that forks inside a branch take" % N.GEN_DRAWS)
+        col = self._param_column(name, low, high, default)
+        reg = len(self._tr_draws)
+        self._tr_draws.append((low, high - 1))
+        self._tr_params[name] = (reg, low, high)
+        self._tr_ops.append((reg | self._tr_guard, 1, N.GEN_PARAM, low, col, high, 0, None))
+        self._tr_late[len(self._tr_ops) - 1] = [("param", reg, col, low, high)]
+        return GenDraw(reg)
+
+    def _param_column(self, name, low, high, default):
+        """the table column of parameter `name`: its own from the first time `_gen_grid` names it on, filled with `default`
+        then; the values set since survive every later recording"""
+        d = self._param_decl.get(name)
+        if d is None:
+            if len(self._param_decl) >= N.GEN_DRAWS:
+                raise NotImplementedError("_gen_grid has named more than %d parameters: the table has %d columns (MG_GEN_DRAWS)"
+                                          % (N.GEN_DRAWS, N.GEN_DRAWS))
+            if self.params_t is None:
+                if self._dry:
+                    self.params_t = np.zeros((self.batch_size, N.GEN_DRAWS), np.uint8)
+                else:
+                    import torch
+                    self._param_buf = torch.zeros(self.cells_stride + self.batch_size * N.GEN_DRAWS, dtype=torch.uint8,
+                                                  device=self.device)
+                    self.params_t = self._param_buf[self.cells_stride:].view(self.batch_size, N.GEN_DRAWS)
+            d = self._param_decl[name] = dict(col=len(self._param_decl), lo=low, hi=high, default=default)
+            if self._dry:
+                self.params_t[:, d["col"]] = default
+            else:
+                self.params_t[:, d["col"]].fill_(default)
+        else:
+            d.update(lo=low, hi=high, default=default)      # (what the table holds is clamped to the interval where it is loaded)
+        return d["col"]
+
+    @property
+    def params(self):
+        """name -> (B,) uint8: the column of the parameter table that `_gen_grid`'s `self._param(name, ...)` reads (a view:
+        `set_params` validates what it writes, a direct write is clamped on the device when it is loaded)"""
+        self._ensure_recorded()
+        return {name: self.params_t[:, d["col"]] for name, d in self._param_decl.items()}
+
+    @_on_device
+    def _ensure_recorded(self):
+        """the recording that follows the constructor (a subclass stores its settings after the base constructor's reset)"""
+        if getattr(self, "_retrace", False):
+            template, ops = self._trace_gen_grid()
+            if self._dry:
+                self._dry_trace = (template, ops)
+            else:
+                self._sync_tables()
+                self._reset_prog = self._program(template, ops)
+            self._retrace = False
+
+    @_on_device
+    def set_params(self, env_mask=None, env_ids=None, **values):
+        """Set per-env parameters of `_gen_grid` (`self._param`): `name=value` with an int, or an array / tensor of one value
+        per env — (B,), or with `env_ids` (k,) — for every env, those of `env_mask` ((B,) bool) or those listed in `env_ids`.
+        Host values are checked against the parameter's interval (ValueError); a device tensor is clamped to it in stream
+        order, without a host synchronisation.  A value takes effect when its env next resets — reset(), the reset inside a
+        step launch, a next-step reset —: the running episode is untouched."""
+        if env_mask is not None and env_ids is not None:
+            raise ValueError("set_params: env_mask or env_ids, not both")
+        self._ensure_recorded()
+        B = self.batch_size
+        for name in values:
+            if name not in self._param_decl:
+                raise KeyError("set_params: %r is no parameter of this env's _gen_grid (declared: %s)"
+                               % (name, ", ".join(sorted(self._param_decl)) or "none"))
+        torch = None
+        if not self._dry:
+            import torch
+        if env_mask is not None:
+            if torch is not None and torch.is_tensor(env_mask):
+                mask = env_mask.to(self.device).bool()
+            else:
+                mask = np.asarray(env_mask).astype(bool)
+            if tuple(mask.shape) != (B,):
+                raise ValueError("env_mask must have shape (batch_size,)")
+            if torch is not None and not torch.is_tensor(mask):
+                mask = torch.from_numpy(mask).to(self.device)
+        if env_ids is not None:
+            if torch is not None and torch.is_tensor(env_ids):
+                ids = env_ids.to(self.device).long()
+            else:
+                ids = np.asarray(env_ids).astype(np.int64).reshape(-1)
+                if ids.size and (ids.min() < 0 or ids.max() >= B):
+                    raise ValueError("set_params: env_ids outside 0..%d" % (B - 1))
+                if torch is not None:
+                    ids = torch.from_numpy(ids).to(self.device)
+            k = int(ids.shape[0])
+        for name, v in values.items():
+            d = self._param_decl[name]
+            col = self.params_t[:, d["col"]]
+            if torch is not None and torch.is_tensor(v) and v.is_cuda:
+                v = v.to(self.device).clamp(d["lo"], d["hi"] - 1).to(torch.uint8)
+            else:
+                v = np.asarray(v.cpu() if torch is not None and torch.is_tensor(v) else v)
+                if v.dtype.kind not in "iu" or v.dtype == bool:
+                    raise ValueError("set_params(%s=): integer values, not %s" % (name, v.dtype))
+                if v.size and (v.min() < d["lo"] or v.max() >= d["hi"]):
+                    raise ValueError("set_params(%s=): values %d..%d outside the parameter's interval [%d, %d)"
+                                     % (name, v.min(), v.max(), d["lo"], d["hi"]))
+                v = v.astype(np.uint8)
+                if torch is not None:
+                    v = torch.from_numpy(v if v.ndim == 0 else np.ascontiguousarray(v)).to(self.device)     # (ascontiguousarray: ndim >= 1)
+            want = (B,) if env_ids is None else (k,)
+            if v.ndim == 1 and env_ids is not None and tuple(v.shape) == (B,) != want:
+                v = v[ids]
+            if v.ndim != 0 and tuple(v.shape) != want:
+                raise ValueError("set_params(%s=): an int or one value per env, shape %s; got %s" % (name, want, tuple(v.shape)))
+            if env_ids is not None:
+                col[ids] = v
+            elif env_mask is not None:
+                if torch is not None:
+                    col.copy_(torch.where(mask, v, col))
+                else:
+                    col[...] = np.where(mask, v, col)
+            elif torch is not None:
+                col.copy_(v.expand(B) if v.ndim == 0 else v)
+            else:
+                col[...] = v
 
     # ---- branching on a draw: one recorded run of `_gen_grid` per path, merged into one guarded program --------------
     def _fork(self, d):
@@ -1364,12 +1514,26 @@ class MultiGridEnv(object):
                 t[x, y] = 1 if reject_fn(np.array([x, y])) else 0
         return t
 
-    def place_obj(self, obj, top=None, size=None, reject_fn=None, max_tries=1e5, env_mask=None):
+    def place_obj(self, obj, top=None, size=None, reject_fn=None, max_tries=1e5, env_mask=None, count=1):
         """Rejection-sample a free cell for `obj` (base.py:690-708).  Inside `_gen_grid` this records
         one placement; the draw happens on the device, per env.  `reject_fn(pos)` is tabulated over the
-        sampling rectangle once (see `_reject_table`)."""
+        sampling rectangle once (see `_reject_table`).  `count` (not upstream's; inside `_gen_grid` only): that many
+        placements in a row — an int is the same as so many calls, a `_rand_int` / `_param` value is a count that every env
+        evaluates for itself at its reset (never below 0, proved when recorded)."""
         if not self._tracing:
+            if isinstance(count, GenDraw) or count != 1:
+                raise NotImplementedError("place_obj(count=) is for the recorded placements of _gen_grid")
             return self._place_live(obj, top, size, max_tries, env_mask, reject_fn)
+        if isinstance(count, GenDraw):
+            if any(c < 0 for c, in self._tr_cases(count)):
+                raise ValueError("place_obj(count=%r): below 0 for some value the draws can take" % (count,))
+            n_rec = count.encode()
+        else:
+            n_rec = GenDraw._int(count, "place_obj(count=%s)" % type(count).__name__)
+            if n_rec < 0:
+                raise ValueError("place_obj(count=%d): a count is not negative" % n_rec)
+            if n_rec == 0:
+                return None
         if isinstance(obj, GridAgentInterface):
             raise NotImplementedError("inside _gen_grid agents are placed by reset() itself")
         max_tries = int(max(1, min(max_tries, 1e5)))
@@ -1381,14 +1545,15 @@ class MultiGridEnv(object):
             operands = region = self._place_region(top, size)
         rej = self._reject_table(reject_fn, region)
         key |= self._tr_guard
-        op = (key, 1, max_tries) + operands + (None if rej is None else rej.tobytes(),)
+        op = (key, n_rec, max_tries) + operands + (None if rej is None else rej.tobytes(),)
         x0, y0, x1, y1 = region
         may = self._tr_grid._shadow[x0:x1, y0:y1] == 0          # (only empty cells accept a placement, base.py:672-679)
         if rej is not None:
             may &= rej[x0:x1, y0:y1] == 0
         self._tr_grid._maybe[x0:x1, y0:y1] |= may
-        if self._tr_ops and self._tr_ops[-1][0] == key and self._tr_ops[-1][2:] == op[2:] and self._tr_ops[-1][2] > 0:
-            self._tr_ops[-1] = (key, self._tr_ops[-1][1] + 1) + op[2:]
+        if (self._tr_ops and self._tr_ops[-1][0] == key and self._tr_ops[-1][2:] == op[2:] and self._tr_ops[-1][2] > 0
+                and not (self._tr_ops[-1][1] | n_rec) & N.GEN_SYM):      # (a symbolic count is an op of its own)
+            self._tr_ops[-1] = (key, self._tr_ops[-1][1] + n_rec) + op[2:]
         else:
             self._tr_ops.append(op)
         return None
@@ -1629,15 +1794,26 @@ class MultiGridEnv(object):
     def _program(self, template, ops):
         import torch
         key = (template.tobytes(), tuple(ops))
+        # a program with a PARAM op reads the env's parameter table right behind its template: all such programs of this env
+        # share ONE buffer — template, then table —, whose head is rewritten (in stream order) when the template changes
+        has_param = any(op[2] == N.GEN_PARAM for op in ops)
+        if has_param and self._param_tpl != key[0]:
+            t = np.zeros(self.cells_stride, np.uint8)
+            t[:self.width * self.height] = template.reshape(-1)
+            self._param_buf[:self.cells_stride].copy_(torch.from_numpy(t).to(self.device))
+            self._param_tpl = key[0]
         prog = self._prog_cache.get(key)
         if prog is not None:
             return prog
-        t = np.zeros(self.cells_stride, np.uint8)
-        t[:self.width * self.height] = template.reshape(-1)
         prog = N.GenProgram()
         # the struct carries a raw device pointer: the tensor it points at is kept on the struct
         # itself, so it lives exactly as long as any holder of the program (cache, `_reset_prog`)
-        prog._template_dev = torch.from_numpy(t).to(self.device)
+        if has_param:
+            prog._template_dev = self._param_buf
+        else:
+            t = np.zeros(self.cells_stride, np.uint8)
+            t[:self.width * self.height] = template.reshape(-1)
+            prog._template_dev = torch.from_numpy(t).to(self.device)
         prog.template_grid = prog._template_dev.data_ptr()
         prog.n_ops = len(ops)
         tables = []                   # place_obj(reject_fn=) tables, one row of cells_stride bytes each
@@ -1648,8 +1824,9 @@ class MultiGridEnv(object):
             guard, low = obj & ~0xFF, obj & 0xFF
             assert guard == 0 or (guard & ~0x07FFFF00 == N.GEN_GUARD
                                   and (guard >> N.GEN_GUARD_LO_SHIFT) & 0xFF <= (guard >> N.GEN_GUARD_HI_SHIFT) & 0xFF)
-            if max_tries < 0:       # a `_rand_int` draw: obj is its register
-                assert 0 <= low < N.GEN_DRAWS
+            if max_tries < 0:       # a `_rand_int` draw, or a PARAM load: obj is its register, y0 a PARAM's table column
+                assert 0 <= low < N.GEN_DRAWS and max_tries in (-1, N.GEN_PARAM)
+                assert max_tries == -1 or (0 <= y0 < N.GEN_DRAWS and 0 <= x0 < x1 <= 256)
             else:
                 assert (1 if max_tries > 0 else 0) <= low < len(self.obj_reg.objs) and count >= 0
                 # (a rectangle with a draw operand was proved by the recorder and is clamped on the device)
@@ -1742,13 +1919,9 @@ class MultiGridEnv(object):
             # obs is rendered (their returned obs is the first obs of the new episode; `done` still
             # reports the end): the lane that computes an env's done flag runs its reset — no host sync,
             # no second launch.
-            if self._retrace:
-                # first step after construction: subclass constructors finish configuring the
-                # scenario after the base constructor's reset (cluttered.py:13-20)
-                template, ops = self._trace_gen_grid()
-                self._sync_tables()
-                self._reset_prog = self._program(template, ops)
-                self._retrace = False
+            # first step after construction: subclass constructors finish configuring the
+            # scenario after the base constructor's reset (cluttered.py:13-20)
+            self._ensure_recorded()
             prog = C.byref(self._reset_prog)
         probe = self._probe          # bench.py: records an event on the launch stream around each launch
         if probe is not None:
@@ -2147,12 +2320,18 @@ class MultiGridEnv(object):
             sd["prestige_t"] = self.prestige_t.clone()
         if self.ep_return_t is not None:        # episode_info: the running episodes' return accumulators
             sd["ep_return_t"] = self.ep_return_t.clone()
+        if self._params_declared():             # `_gen_grid` names parameters: the table they are read from
+            sd["params_t"] = self.params_t.clone()
         sd["version"] = torch.tensor(STATE_DICT_VERSION)
         return sd
+
+    def _params_declared(self):
+        return bool(self._param_decl)
 
     def load_state_dict(self, sd):
         want = set(self._STATE_KEYS) | {"version"} | ({"prestige_t"} if self.prestige_t is not None else set())
         want |= {"ep_return_t"} if self.ep_return_t is not None else set()
+        want |= {"params_t"} if self._params_declared() else set()
         if set(sd.keys()) != want:
             raise KeyError("load_state_dict: expected exactly the keys %s, got %s (a checkpoint without "
                            "'version' / 'mt_head' predates the look-ahead RNG form and cannot be resumed)"

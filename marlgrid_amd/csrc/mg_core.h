@@ -523,7 +523,20 @@ MG_HD int reset_env(const MgConfig& cfg, const MgState& st, const MgGenProgram& 
         if (sym && op.max_tries > 0 && (op.x1 <= op.x0 || op.y1 <= op.y0)) { err = MG_ERR_VALUE; break; }   // randint(low >= high)
         if (op.max_tries < 0) {       // draw[obj] = _rand_int(x0, x1) = np_random.randint(x0, x1); a one-value range draws nothing
             const int span = op.x1 - op.x0 - 1;
-            const uint32_t v = (uint32_t)(op.x0 + (int)mt.bounded((uint32_t)(span < 0 ? 0 : span))) & 0xFFu;
+            uint32_t v;
+            if (op.max_tries == MG_GEN_PARAM) {
+                // ... or a PARAMETER of this env: column y0 of the byte table behind the template, clamped to the declared
+                // interval [x0, x1) — whatever bytes the table holds, the register stays inside what the recorder proved; no
+                // RNG word.  (template_grid is never redirected to an LDS copy, unlike ops: the table hangs there)
+                // (the row's address is made here, from `b` as it is now: hoisted out of the op loop it is two registers per lane
+                // across every RNG refill of the reset)
+                const uint32_t row = keep_packed((uint32_t)b) * MG_GEN_DRAWS + (uint32_t)cfg.cells_stride;
+                const int p = prog.template_grid[(size_t)row + (size_t)(op.y0 & (MG_GEN_DRAWS - 1))];
+                const int hi = op.x0 + (span < 0 ? 0 : span);
+                v = (uint32_t)(p < op.x0 ? op.x0 : p > hi ? hi : p) & 0xFFu;
+            } else {
+                v = (uint32_t)(op.x0 + (int)mt.bounded((uint32_t)(span < 0 ? 0 : span))) & 0xFFu;
+            }
             const int sh = (op.obj & (MG_GEN_DRAWS - 1)) * 8;
             draws = (draws & ~(0xFFull << sh)) | ((uint64_t)v << sh);
             continue;
@@ -537,7 +550,11 @@ MG_HD int reset_env(const MgConfig& cfg, const MgState& st, const MgGenProgram& 
         // agent is on the fresh grid yet)
         // (the rectangle is per env now: x0 | y0 << 8 | (x1 - x0 - 1) << 16 | (y1 - y0 - 1) << 24 — W, H <= 255 — in one register)
         uint32_t rect = (uint32_t)op.x0 | (uint32_t)op.y0 << 8 | (uint32_t)(op.x1 - op.x0 - 1) << 16 | (uint32_t)(op.y1 - op.y0 - 1) << 24;
-        for (int c = 0; c < op.count && !err; c++) {
+        // the count may be `const +- draw[r]` too — that many consecutive place_obj calls, below 0 is none —, so it is a lane's
+        // own: what is left of it and the error share ONE register across the RNG refills (err is 0 here; codes fit 4 bits)
+        const int cnt = gen_operand(op.count, draws);
+        uint32_t left_err = (uint32_t)(cnt < 0 ? 0 : cnt) << 4;
+        while (left_err >= 16u && !(left_err & 15u)) {
             bool ok = false;
             for (int t = 0; t < op.max_tries; t++) {
                 rect = keep_packed(rect);
@@ -548,8 +565,9 @@ MG_HD int reset_env(const MgConfig& cfg, const MgState& st, const MgGenProgram& 
                 if (op.reject >= 0 && prog.reject[(size_t)op.reject * cfg.cells_stride + cell]) continue;   // reject_fn(pos)
                 if (g[cell] == 0) { g[cell] = (uint8_t)op.obj; ok = true; break; }
             }
-            if (!ok) err = MG_ERR_RECURSION;
+            left_err = keep_packed((left_err - 16u) | (ok ? 0u : (uint32_t)MG_ERR_RECURSION));
         }
+        err = (int)(left_err & 15u);
     }
     for (int k = 0; k < n; k++) {
         uint64_t nr = 0;
@@ -1160,6 +1178,8 @@ MG_HD void reset_run(const MgConfig& cfg, const MgState& st, const MgGenProgram&
     Mt mt{st.mt + (size_t)b * MG_MT_N, st.mt_pos[b], head, 1, 0};
     for (int k = 0; k < n; k++) rec[k * S + col] = st.agents[(size_t)b * n + k];
     const int err = reset_env(cfg, st, prog, oflags, b, g, mt, rec, S, col);
+    // (the addresses below are made again from `b`, not carried in registers across the whole reset)
+    b = (int)keep_packed((uint32_t)b);
     for (int k = 0; k < n; k++) st.agents[(size_t)b * n + k] = rec[k * S + col];
     mt_finish(mt, head);
     st.mt_pos[b] = mt.pos;

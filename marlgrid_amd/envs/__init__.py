@@ -10,7 +10,9 @@ draw (`draw +- int`) and use it as a coordinate or extent of put_obj / grid.set 
 `size` and as a bound of a later `_rand_int`.  To BRANCH on one (compare it, index or loop with it, choose an object by
 it) `_gen_grid` asks for its value with `self._fork(draw)`, or draws with `self._rand_elem(...)` / `self._rand_bool()`: it is
 then recorded once per path and every env runs the ops of its own path (`ColoredDoorKeyEnv`: a door and key of one of six
-colours).  It still cannot put a draw into `agent_spawn_kwargs` or have a `reject_fn` that depends on one.  Upstream registers
+colours).  `self._param(name, lo, hi)` is used like a draw but read per env from `env.params[name]` (`env.set_params`) at every
+reset: `ClutteredMultiGrid(n_clutter_max=K)` scatters `count=self._param("n_clutter", 0, K + 1)` blocks.  `_gen_grid` still
+cannot put a draw or a parameter into `agent_spawn_kwargs` or have a `reject_fn` that depends on one.  Upstream registers
 no DoorKey id; the ids in `extension_envs` are this package's own and are built by `make` like the registered ones.
 """
 import functools
@@ -124,4 +126,7 @@ for _row in (("MarlGrid-2AgentDoorKey6x6-v0", 6), ("MarlGrid-2AgentDoorKey8x8-v0
     register_marl_env(_row[0], DoorKeyEnv, n_agents=2, grid_size=_row[1], view_size=7, listed_in=extension_envs)
 register_marl_env("MarlGrid-2AgentColoredDoorKey8x8-v0", ColoredDoorKeyEnv, n_agents=2, grid_size=8, view_size=7,
                   listed_in=extension_envs)
+# a curriculum over the clutter: every env reads its number of wall blocks, 0 .. 50, from `env.params["n_clutter"]` when it resets
+register_marl_env("MarlGrid-3AgentClutteredCurriculum15x15-v0", ClutteredMultiGrid, n_agents=3, grid_size=15, view_size=7,
+                  env_kwargs=dict(n_clutter=25, n_clutter_max=50), listed_in=extension_envs)
 del _row

@@ -64,11 +64,16 @@ class ClutteredMultiGrid(_WalledRoom):
     at random; the goal sits in the corner unless `randomize_goal`."""
     mission = "get to the green square"
 
-    def __init__(self, *args, n_clutter=None, clutter_density=None, randomize_goal=False, **kwargs):
+    def __init__(self, *args, n_clutter=None, clutter_density=None, randomize_goal=False, n_clutter_max=None, **kwargs):
         _require_one_of(n_clutter, clutter_density)
         super().__init__(*args, **kwargs)          # resets once with the defaults read below
         self.n_clutter = _clutter_count(self, n_clutter, clutter_density)
         self.randomize_goal = randomize_goal
+        if n_clutter_max is not None:
+            # (not upstream's) the number of blocks is a per-env parameter, 0 .. n_clutter_max: `env.set_params(n_clutter=...)`;
+            # `n_clutter` is what every env starts with.  Recorded now, so that the parameter is there to be set
+            self.n_clutter_max = int(n_clutter_max)
+            self._ensure_recorded()
 
     def _gen_grid(self, width, height):
         self._room(width, height)
@@ -76,7 +81,10 @@ class ClutteredMultiGrid(_WalledRoom):
             self.place_obj(Goal(color="green", reward=1), max_tries=100)
         else:
             self._corner_goal(width, height)
-        self._scatter(Wall, getattr(self, "n_clutter", 0))
+        if getattr(self, "n_clutter_max", None) is None:
+            self._scatter(Wall, getattr(self, "n_clutter", 0))
+        else:
+            self.place_obj(Wall(), max_tries=100, count=self._param("n_clutter", 0, self.n_clutter_max + 1, default=self.n_clutter))
         self._spawn_anywhere()
 
 

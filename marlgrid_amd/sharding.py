@@ -62,7 +62,7 @@ def _engine_version():
 def merge_state_dicts(dicts):
     """`MultiGridEnv.state_dict()`s of consecutive slices of a batch -> the state_dict of the whole batch: every tensor
     concatenated along dim 0 in the order given, `version` checked (equal everywhere, and the one this engine reads).  The
-    optional keys (`prestige_t`, `ep_return_t`) are in every dict or in none: anything else raises KeyError.  Pure: no
+    optional keys (`prestige_t`, `ep_return_t`, `params_t`) are in every dict or in none: anything else raises KeyError.  Pure: no
     device is touched beyond what torch.cat does with the tensors it is given (all on one device)."""
     import torch
     dicts = list(dicts)
@@ -99,6 +99,54 @@ def split_state_dict(sd, ranges):
         if k != "version" and v.shape[0] != at:
             raise ValueError("split_state_dict: %s has %d rows, the ranges cover %d" % (k, v.shape[0], at))
     return [dict({k: v[lo:hi] for k, v in sd.items() if k != "version"}, version=sd["version"].clone()) for lo, hi in ranges]
+
+
+def split_params(ranges, env_mask=None, env_ids=None, **values):
+    """`MultiGridEnv.set_params` arguments in GLOBAL env order -> one dict of keyword arguments per (lo, hi) of `ranges` (None
+    for a shard that none of `env_ids` falls into): rows lo .. hi of `env_mask` and of every per-env value, `env_ids` of the
+    shard rebased to it together with their values.  `env_ids` are read on the host (a device tensor is copied: a host
+    sync); masks and values may stay on their device — they are only sliced."""
+    import numpy as np
+    ranges = [(int(lo), int(hi)) for lo, hi in ranges]
+    B = ranges[-1][1]
+    if env_mask is not None and env_ids is not None:
+        raise ValueError("set_params: env_mask or env_ids, not both")
+    if env_mask is not None and tuple(env_mask.shape if hasattr(env_mask, "shape") else np.shape(env_mask)) != (B,):
+        raise ValueError("env_mask must have shape (batch_size,)")
+    ids = None
+    if env_ids is not None:
+        ids = np.asarray(env_ids.cpu() if hasattr(env_ids, "cpu") else env_ids).astype(np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= B):
+            raise ValueError("set_params: env_ids outside 0..%d" % (B - 1))
+
+    def shape(v):
+        return tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
+    for name, v in values.items():
+        want = (B,) if ids is None else (len(ids),)
+        if shape(v) not in ((), want, (B,)):
+            raise ValueError("set_params(%s=): an int or one value per env, shape %s; got %s" % (name, want, shape(v)))
+    out = []
+    for lo, hi in ranges:
+        kw = {}
+        if env_mask is not None:
+            kw["env_mask"] = env_mask[lo:hi]
+        sel = None
+        if ids is not None:
+            sel = np.nonzero((ids >= lo) & (ids < hi))[0]
+            if not sel.size:
+                out.append(None)
+                continue
+            kw["env_ids"] = ids[sel] - lo
+        for name, v in values.items():
+            if shape(v) == ():
+                kw[name] = v
+            elif ids is not None and shape(v) == (len(ids),):
+                v = v if hasattr(v, "shape") else np.asarray(v)
+                kw[name] = v[sel] if isinstance(v, np.ndarray) else v[sel.tolist()]
+            else:
+                kw[name] = (v if hasattr(v, "shape") else np.asarray(v))[lo:hi]
+        out.append(kw)
+    return out
 
 
 def max_over_ranks(value, device=None):
@@ -174,6 +222,17 @@ class _Shards(object):
         `state_dict()` has at this batch size (`merge_state_dicts` of the shards').  It loads into that env, and into any
         other split of the batch — `load_state_dict` of a ShardPipeline or a DeviceShards with other shards.  Host sync."""
         return merge_state_dicts(self._each(lambda k, env: {key: v.cpu() for key, v in env.state_dict().items()}))
+
+    def set_params(self, env_mask=None, env_ids=None, **values):
+        """`MultiGridEnv.set_params` for the whole batch: `env_mask`, `env_ids` and per-env values in GLOBAL env order, split
+        by `ranges` (`split_params`); every shard's part is written on its own stream"""
+        parts = split_params(self.ranges, env_mask=env_mask, env_ids=env_ids, **values)
+        self._each(lambda k, env: None if parts[k] is None else env.set_params(**parts[k]))
+
+    @property
+    def params(self):
+        """per shard: its env's `params` (name -> the shard's (rows,) uint8 column)"""
+        return [env.params for env in self.envs]
 
     def load_state_dict(self, sd):
         """a checkpoint of the whole batch (from one env, a pipeline or device shards, however it was split), rows

@@ -288,6 +288,32 @@ int32_t mg_mt_seed(int32_t B, const uint32_t* keys, const int32_t* key_len, uint
 int32_t mg_reset(const MgConfig* cfg, const MgState* st, const MgGenProgram* prog,
                  const uint8_t* env_mask, void* stream);
 
+/* Replayable levels: a level is a seed, and playing it is `env.seed(s); env.reset()` (base.py:371-374) — the episode that
+ * follows a generator freshly seeded with s.  A bank holds such generators: bank_mt uint32 [L][624], bank_pos int32 [L],
+ * bank_head uint32 [L][16] (what mg_mt_seed writes per env), bank_seed int64 [L] with -1 = empty slot; bank_mt and bank_head
+ * 16-byte aligned.  All device memory, caller-owned.
+ *
+ * mg_level_seed: row i of n puts seeds[i] (device int64) into slot slots[i] (device int64 [n]; NULL: slot i), hashing the
+ * seed on the device as gym's seeding.np_random does.  row_mask: device uint8 [n] or NULL (= all), rows with mask != 0 only.
+ * A seed < 0 empties the slot (bank_seed = -1, generator untouched); a slot outside [0, n_slots) is skipped; two rows of one
+ * call naming one slot are the caller's error. */
+int32_t mg_level_seed(int32_t n, const int64_t* seeds, const int64_t* slots, const uint8_t* row_mask, int32_t n_slots,
+                      uint32_t* bank_mt, int32_t* bank_pos, uint32_t* bank_head, int64_t* bank_seed, void* stream);
+/* mg_level_apply (base.py:371-374), in front of the launch that resets: every *selected* env b whose level_of_env[b] (device
+ * int64 [B]) names a filled slot gets that slot's generator in place of its own (st->mt, mt_pos, mt_head), its agents'
+ * headings set to 0 (a reset keeps them: the level starts as in an env made for it) and episode_level[b] = bank_seed[slot]; a selected env whose level is < 0, >= n_slots or empty keeps its running stream and
+ * gets episode_level[b] = -1 (free-running).  Selected by `rule`: MG_LEVEL_PENDING — the envs whose episode has ended, read
+ * off the state as the next-step reset of mg_*_ep reads it (never st->done) —, MG_LEVEL_MASK — env_mask as mg_reset takes
+ * it —, MG_LEVEL_PUBLISH — none.  Last, out_level[b] = episode_level[b] for every env (out_level: device int64 [B] or NULL).
+ * Only B, n_agents and max_steps of cfg are read. */
+#define MG_LEVEL_PUBLISH 0
+#define MG_LEVEL_PENDING 1
+#define MG_LEVEL_MASK 2
+int32_t mg_level_apply(const MgConfig* cfg, const MgState* st, int32_t rule, const uint8_t* env_mask,
+                       const int64_t* level_of_env, int32_t n_slots, const uint32_t* bank_mt, const int32_t* bank_pos,
+                       const uint32_t* bank_head, const int64_t* bank_seed, int64_t* episode_level, int64_t* out_level,
+                       void* stream);
+
 /* actions: device [B][n_agents], element size `action_bytes` in {1,4,8} (little-endian ints).
  * rewards: device float32 [B][n_agents].  Sets st->done[b].
  * auto_reset: NULL, or the reset program: an env whose episode ends in this step (done[b] = 1) starts

@@ -105,6 +105,8 @@ class PlaceStats(C.Structure):
                 ("all_ms", C.c_float * PLACE_ALL)]
 
 
+LEVEL_PUBLISH, LEVEL_PENDING, LEVEL_MASK = 0, 1, 2      # MG_LEVEL_* (mg_level_apply's rule)
+
 DELTA_FORCE = 1            # MG_DELTA_FORCE (mg_step_render_delta)
 
 SPEC_COMPILE_ONLY = 1      # MG_SPEC_COMPILE_ONLY (mg_render_specialize)
@@ -139,7 +141,8 @@ SYMBOLS = ["mg_abi_version", "mg_struct_sizes", "mg_host_flag_alloc", "mg_host_f
            "mg_episode_struct_size", "mg_step_ep", "mg_step_render_ep", "mg_step_encode_views_ep",
            "mg_step_render_delta", "mg_step_render_delta_ex",
            "mg_spec_info_struct_size", "mg_render_specialize", "mg_step_render_spec", "mg_render_obs_spec",
-           "mg_render_spec_release", "mg_rtc_source"]
+           "mg_render_spec_release", "mg_rtc_source",
+           "mg_level_seed", "mg_level_apply"]
 
 _lib = None
 _path = LIB_PATH
@@ -204,6 +207,10 @@ def lib():
     L.mg_error_string.argtypes = [i32]
     L.mg_build_info.restype = C.c_char_p
     L.mg_mt_seed.argtypes = [i32, vp, vp, vp, vp, vp, vp]
+    # (n, seeds, slots, row_mask, n_slots, bank_mt, bank_pos, bank_head, bank_seed, stream)
+    L.mg_level_seed.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    # (cfg, st, rule, env_mask, level_of_env, n_slots, bank_mt, bank_pos, bank_head, bank_seed, episode_level, out_level, stream)
+    L.mg_level_apply.argtypes = [C.POINTER(Config), C.POINTER(State), i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.mg_reset.argtypes = [C.POINTER(Config), C.POINTER(State), C.POINTER(GenProgram), vp, vp]
     L.mg_step.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp]
     L.mg_step_render.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp]

@@ -143,6 +143,29 @@ int32_t mg_reset(const MgConfig* cfg, const MgState* st, const MgGenProgram* pro
     return rc(mg::launch_reset(*cfg, *st, *prog, env_mask, (hipStream_t)stream));
 }
 
+int32_t mg_level_seed(int32_t n, const int64_t* seeds, const int64_t* slots, const uint8_t* row_mask, int32_t n_slots,
+                      uint32_t* bank_mt, int32_t* bank_pos, uint32_t* bank_head, int64_t* bank_seed, void* stream) {
+    if (n < 0 || n_slots < 0 || !seeds || !bank_mt || !bank_pos || !bank_head || !bank_seed) return MG_E_ARG;
+    return rc(mg::launch_level_seed(n, seeds, slots, row_mask, n_slots, bank_mt, bank_pos, bank_head, bank_seed, (hipStream_t)stream));
+}
+
+int32_t mg_level_apply(const MgConfig* cfg, const MgState* st, int32_t rule, const uint8_t* env_mask, const int64_t* level_of_env,
+                       int32_t n_slots, const uint32_t* bank_mt, const int32_t* bank_pos, const uint32_t* bank_head,
+                       const int64_t* bank_seed, int64_t* episode_level, int64_t* out_level, void* stream) {
+    if (!cfg || cfg->B < 0 || cfg->n_agents < 1 || cfg->n_agents > MG_MAX_AGENTS) return MG_E_ARG;
+    const int e = check_state(st);
+    if (e) return e;
+    if (rule != MG_LEVEL_PUBLISH && rule != MG_LEVEL_PENDING && rule != MG_LEVEL_MASK) return MG_E_ARG;
+    if (n_slots < 0 || !episode_level) return MG_E_ARG;
+    if (rule != MG_LEVEL_PUBLISH && (!level_of_env || (n_slots > 0 && (!bank_mt || !bank_pos || !bank_head || !bank_seed)))) return MG_E_ARG;
+    // (the copy is 16-byte traffic: generator rows are 2 496 and 64 bytes, so aligned bases keep every row aligned)
+    if ((reinterpret_cast<uintptr_t>(bank_mt) | reinterpret_cast<uintptr_t>(bank_head) | reinterpret_cast<uintptr_t>(st->mt) |
+         reinterpret_cast<uintptr_t>(st->mt_head)) & 15)
+        return MG_E_ARG;
+    return rc(mg::launch_level_apply(*cfg, *st, rule, env_mask, level_of_env, n_slots, bank_mt, bank_pos, bank_head, bank_seed,
+                                     episode_level, out_level, (hipStream_t)stream));
+}
+
 int32_t mg_episode_struct_size(void) { return (int32_t)sizeof(MgEpisode); }
 
 int32_t mg_step_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,

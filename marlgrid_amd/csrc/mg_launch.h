@@ -34,4 +34,10 @@ hipError_t launch_place(const MgConfig& cfg, const MgState& st, int what, int x0
                         uint8_t* out_ok, hipStream_t s);
 hipError_t launch_frame(const MgConfig& cfg, const MgState& st, const int32_t* env_ids, int K, const uint8_t* atlas,
                         int ts, int highlight, uint32_t amax, uint8_t* out, hipStream_t s);
+// replayable levels (mg_levels.hip): seed rows of a bank of generators; hand the envs that reset their level's generator
+hipError_t launch_level_seed(int n, const int64_t* seeds, const int64_t* slots, const uint8_t* mask, int n_slots, uint32_t* bank_mt,
+                             int32_t* bank_pos, uint32_t* bank_head, int64_t* bank_seed, hipStream_t s);
+hipError_t launch_level_apply(const MgConfig& cfg, const MgState& st, int rule, const uint8_t* mask, const int64_t* level_of_env,
+                              int n_slots, const uint32_t* bank_mt, const int32_t* bank_pos, const uint32_t* bank_head,
+                              const int64_t* bank_seed, int64_t* episode_level, int64_t* out_level, hipStream_t s);
 }  // namespace mg

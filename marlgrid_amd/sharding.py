@@ -62,7 +62,7 @@ def _engine_version():
 def merge_state_dicts(dicts):
     """`MultiGridEnv.state_dict()`s of consecutive slices of a batch -> the state_dict of the whole batch: every tensor
     concatenated along dim 0 in the order given, `version` checked (equal everywhere, and the one this engine reads).  The
-    optional keys (`prestige_t`, `ep_return_t`, `params_t`) are in every dict or in none: anything else raises KeyError.  Pure: no
+    optional keys (`prestige_t`, `ep_return_t`, `params_t`, and `episode_level_t` with `level_next_t`) are in every dict or in none: anything else raises KeyError.  Pure: no
     device is touched beyond what torch.cat does with the tensors it is given (all on one device)."""
     import torch
     dicts = list(dicts)
@@ -149,6 +149,19 @@ def split_params(ranges, env_mask=None, env_ids=None, **values):
     return out
 
 
+def split_levels(ranges, ids=None, seeds=None, env_mask=None, env_ids=None):
+    """`MultiGridEnv.set_levels` arguments in GLOBAL env order -> one dict of keyword arguments per (lo, hi) of `ranges` (None for
+    a shard that none of `env_ids` falls into), as `split_params` splits a parameter: exactly one of `ids` (bank slots) and
+    `seeds`, an int or one value per env.  The bank is not part of it (a shard reads a replica on its own device)."""
+    if (ids is None) == (seeds is None):
+        raise ValueError("set_levels: either (bank, ids) or seeds=")
+    name, v = ("ids", ids) if ids is not None else ("seeds", seeds)
+    try:
+        return split_params(ranges, env_mask=env_mask, env_ids=env_ids, **{name: v})
+    except ValueError as e:
+        raise ValueError(str(e).replace("set_params", "set_levels")) from None
+
+
 def max_over_ranks(value, device=None):
     """MAX-reduce a python float over the default process group (returns it unchanged when
     torch.distributed is not initialised)."""
@@ -228,6 +241,29 @@ class _Shards(object):
         by `ranges` (`split_params`); every shard's part is written on its own stream"""
         parts = split_params(self.ranges, env_mask=env_mask, env_ids=env_ids, **values)
         self._each(lambda k, env: None if parts[k] is None else env.set_params(**parts[k]))
+
+    def set_levels(self, bank=None, ids=None, seeds=None, env_mask=None, env_ids=None):
+        """`MultiGridEnv.set_levels` for the whole batch: `ids` / `seeds`, `env_mask` and `env_ids` in GLOBAL env order, split by
+        `ranges` (`split_levels`).  With a bank, every shard reads a replica of it on its own device — one per distinct device,
+        seeded there from `bank.seeds` — that `bank.assign` keeps up to date."""
+        if (bank is None) == (seeds is None) or (bank is not None and ids is None) or (seeds is not None and ids is not None):
+            raise ValueError("set_levels: either (bank, ids) or seeds=")
+        parts = split_levels(self.ranges, ids=ids, seeds=seeds, env_mask=env_mask, env_ids=env_ids)
+        reps = [None] * len(self.envs)
+        if bank is not None and not self.envs[0]._dry:
+            for k, env in enumerate(self.envs):
+                reps[k] = bank.replica(env.device, [s for s, e in zip(self.streams, self.envs) if e.device == env.device])
+
+        def one(k, env):
+            env._enable_levels()        # (every shard, selected or not: a checkpoint has the level keys in every shard or in none)
+            if parts[k] is not None:
+                env.set_levels(bank=reps[k] if bank is not None and reps[k] is not None else bank, **parts[k])
+        self._each(one)
+
+    @property
+    def episode_level(self):
+        """per shard: its env's `episode_level`"""
+        return [env.episode_level for env in self.envs]
 
     @property
     def params(self):

@@ -19,28 +19,29 @@ Differences from the reference that the batch forces (documented in DESIGN.md):
     observation space says (the reference actually returns int64 arrays, base.py:305);
   * `_gen_grid` is *recorded* once per reset (walls / put_obj -> static template, place_obj ->
     ordered rejection-sampling program) and replayed on the device for every env with that env's
-    own RNG, so scenario subclasses written against the reference API keep working as long as
-    their layout logic does not branch on random draws in Python;
+    own RNG, so scenario subclasses written against the reference API keep working; layout logic
+    that branches on a random draw in Python says so with `self._fork(draw)` (or draws through
+    `_rand_elem` / `_rand_bool`) and is recorded once per value — the recorder, its op type and the
+    packing of a program are marlgrid_amd/gen_recorder.py;
   * per-env runtime errors (the reference's exceptions) are collected in `error` and raised as the
     matching Python exception after the step (strict=True) or on `check_errors()`.
 """
 import ctypes as C
 import functools
 import os
-import threading
 
 import numpy as np
 
 from . import _native as N
 from . import rendering, seeding, spaces
 from .agents import GridAgentInterface
+from .gen_recorder import GenDraw, GenRecorder, _NO_BRANCH, _any_draw, _gen_add, _trace, decode_program, pack_program
 from .objects import COLOR_TO_IDX, OBJECT_TYPES, BonusTile, Box, Door, Goal, Key, Wall, WorldObj
 
 TILE_PIXELS = 32
 DEFAULT_PLACE_OBS = "search"
 STATE_DICT_VERSION = 3              # the C ABI version that last changed the MgState layout / RNG form the tensors follow
 
-_trace = threading.local()
 
 
 def _on_device(fn):
@@ -56,82 +57,6 @@ def _on_device(fn):
         with torch.cuda.device(self.device):
             return fn(self, *args, **kwargs)
     return wrapper
-
-
-_NO_BRANCH = ("a value of self._rand_int(...) inside _gen_grid is drawn later, per env, on the device: _gen_grid may compute "
-              "with it (draw + k, k + draw, draw - k, k - draw with Python ints) and hand the result to put_obj / grid.set / the "
-              "wall helpers / place_obj(top=, size=) / a later _rand_int, but it cannot branch on it (%s) — self._fork(draw) hands "
-              "its value over as a Python int, one recorded path per value; self._rand_elem(...) / self._rand_bool() draw and fork")
-
-
-class GenDraw(object):
-    """What `self._rand_int(lo, hi)` returns while `_gen_grid` is recorded: `const + sign * draw[reg]`, sign +-1 — a
-    coordinate or extent whose value every env draws for itself at every reset (MgGenOp, MG_GEN_SYM)."""
-    __slots__ = ("reg", "sign", "const")
-    __hash__ = None
-
-    def __init__(self, reg, sign=1, const=0):
-        self.reg, self.sign, self.const = reg, sign, const
-
-    @staticmethod
-    def _int(k, what):
-        if isinstance(k, (bool, GenDraw)) or not isinstance(k, (int, np.integer)):
-            raise NotImplementedError(_NO_BRANCH % what)
-        return int(k)
-
-    def __add__(self, k):
-        return GenDraw(self.reg, self.sign, self.const + self._int(k, "draw + %s" % type(k).__name__))
-    __radd__ = __add__
-
-    def __sub__(self, k):
-        return GenDraw(self.reg, self.sign, self.const - self._int(k, "draw - %s" % type(k).__name__))
-
-    def __rsub__(self, k):
-        return GenDraw(self.reg, -self.sign, self._int(k, "%s - draw" % type(k).__name__) - self.const)
-
-    def _refuse(name):
-        def f(self, *a, **k):
-            raise NotImplementedError(_NO_BRANCH % name)
-        return f
-    for _n in ("eq", "ne", "lt", "le", "gt", "ge", "bool", "int", "index", "float", "mul", "rmul", "floordiv", "rfloordiv",
-               "truediv", "rtruediv", "mod", "rmod", "neg", "pos", "abs", "pow", "rpow", "lshift", "rshift", "and", "or",
-               "xor", "invert", "round", "trunc"):
-        locals()["__%s__" % _n] = _refuse(_n)
-    del _n, _refuse
-
-    def __repr__(self):
-        return "<%d %s draw[%d]>" % (self.const, "+" if self.sign > 0 else "-", self.reg)
-
-    def encode(self):
-        if not -32768 <= self.const <= 32767:
-            raise NotImplementedError("_gen_grid: a constant of %d next to a draw does not fit the program's operand" % self.const)
-        return N.GEN_SYM | (N.GEN_NEG if self.sign < 0 else 0) | (self.reg << N.GEN_DRAW_SHIFT) | (self.const & 0xFFFF)
-
-
-def _gen_add(a, b):
-    """a + b inside the recorder (top + size, x + length): the two may hold the SAME draw with opposite signs"""
-    if isinstance(a, GenDraw) and isinstance(b, GenDraw):
-        if a.reg == b.reg and a.sign + b.sign == 0:
-            return a.const + b.const
-        raise NotImplementedError(_NO_BRANCH % "a sum of two draws")
-    return a + b
-
-
-def _gen_enc(v):
-    return v.encode() if isinstance(v, GenDraw) else int(v)
-
-
-def _any_draw(*vs):
-    return any(isinstance(v, GenDraw) for v in vs)
-
-
-def _same_spawn(a, b):
-    """two `agent_spawn_kwargs` left by two runs of one `_gen_grid` (callables by identity)"""
-    a, b = a or {}, b or {}
-    if set(a) != set(b):
-        return False
-    return all(a[k] is b[k] if callable(a[k]) else (tuple(a[k]) == tuple(b[k]) if isinstance(a[k], (tuple, list)) else a[k] == b[k])
-               for k in a)
 
 
 class ObjectRegistry(object):
@@ -215,6 +140,7 @@ class MultiGrid(object):
             raise ValueError("_gen_grid must build a grid of the env's own (width, height)")
         self.orientation = orientation
         self._env = env
+        self._rec = env._gen
         self.obj_reg = env.obj_reg
         self._template = np.zeros((self.width, self.height), np.uint8)
         # what `_gen_grid` itself has drawn so far — the template plus the static edits made after a place_obj (which go
@@ -223,24 +149,24 @@ class MultiGrid(object):
         # cells a recorded random placement may have filled since `_gen_grid` last drew on them (place_obj only takes empty
         # cells of its sampling rectangle; a later static edit of a cell decides it again)
         self._maybe = np.zeros((self.width, self.height), bool)
-        env._tr_begin(self)
+        self._rec.begin(self)
 
     # ---- layout recording / live edits --------------------------------------------------------
     def set(self, i, j, obj):
-        env = self._env
-        if env._tracing and _any_draw(i, j):
-            env._tr_fill_sym(self.obj_reg.get_key(obj), [(i, j, _gen_add(i, 1), _gen_add(j, 1))])
+        rec = self._rec
+        if rec.active and _any_draw(i, j):
+            rec.fill_sym(self.obj_reg.get_key(obj), [(i, j, _gen_add(i, 1), _gen_add(j, 1))])
             return
         assert i >= 0 and i < self.width
         assert j >= 0 and j < self.height
-        if env._tracing:
+        if rec.active:
             key = self.obj_reg.get_key(obj)
-            if env._tr_static(("put", key, int(i), int(j)), key, [(int(i), int(j), int(i) + 1, int(j) + 1)]):
+            if rec.static(("put", key, int(i), int(j)), key, [(int(i), int(j), int(i) + 1, int(j) + 1)]):
                 self._template[i, j] = key
             self._shadow[i, j] = key
             self._maybe[i, j] = False
         else:
-            env.put_obj(obj, i, j)
+            self._env.put_obj(obj, i, j)
 
     def horz_wall(self, x, y, length=None, obj_type=Wall):
         if length is None:
@@ -270,22 +196,22 @@ class MultiGrid(object):
 
     def _wall_sym(self, obj_type, rects):
         """a wall helper with a draw among its arguments: its rectangles as fills of the reset program"""
-        if not self._env._tracing:
+        if not self._rec.active:
             raise NotImplementedError(_NO_BRANCH % "used outside _gen_grid")
-        self._env._tr_fill_sym(self.obj_reg.get_key(obj_type()), rects)
+        self._rec.fill_sym(self.obj_reg.get_key(obj_type()), rects)
 
     def _wall(self, sym, cells, obj_type, rects):
-        env = self._env
+        rec = self._rec
         # (objects are value types here: every obj_type() of a helper is the same table row.  Walls of Walls are recorded
         # as what they are; a helper drawn with another type is, before the first place_obj, its cells one by one — the
         # template does not care — and after one a handful of rectangle fills in the reset program, not an op per cell)
-        if env._tracing and (obj_type is Wall or env._tr_ops):
+        if rec.active and (obj_type is Wall or rec.in_program):
             key = self.obj_reg.get_key(obj_type())
             for (i, j) in cells:
                 assert 0 <= i < self.width and 0 <= j < self.height
             if obj_type is not Wall:
                 sym = [("put", key, int(i), int(j)) for (i, j) in dict.fromkeys(cells)]
-            if env._tr_static(sym, key, [tuple(int(v) for v in r) for r in rects if r[2] > r[0] and r[3] > r[1]]):
+            if rec.static(sym, key, [tuple(int(v) for v in r) for r in rects if r[2] > r[0] and r[3] > r[1]]):
                 for (i, j) in cells:
                     self._template[i, j] = key
             for (i, j) in cells:
@@ -306,7 +232,7 @@ class MultiGrid(object):
         """the non-agent object kind in cell (i, j) of env `env` (host sync; debugging aid)"""
         assert i >= 0 and i < self.width
         assert j >= 0 and j < self.height
-        if self._env._tracing:      # inside `_gen_grid`: what it has drawn so far (random placements are per env: not in here)
+        if self._rec.active:        # inside `_gen_grid`: what it has drawn so far (random placements are per env: not in here)
             if self._maybe[i, j]:
                 # upstream's grid.get() here sees what an earlier place_obj put into THIS env's cell; the recorder cannot —
                 # the draw happens later, on the device, per env.  Layout code that branches on the answer would be recorded
@@ -772,7 +698,7 @@ class MultiGridEnv(object):
         self.obj_reg = ObjectRegistry()
         self._tables_version = -1
         self._settings_seen = None
-        self._tracing = False
+        self._gen = GenRecorder(self)       # all `_gen_grid` recording state and logic (gen_recorder.py)
         self._prog_cache = {}
         self._param_decl = {}       # `_param` names of this env's `_gen_grid`: name -> dict(col, lo, hi, default); columns stay
         self._param_buf = None      # the template of a program with a PARAM op and, behind it, the table (marlgrid_hip.h)
@@ -1184,57 +1110,6 @@ class MultiGridEnv(object):
     def _gen_grid(self, width, height):
         raise NotImplementedError("subclasses build self.grid here (see marlgrid_amd/envs)")
 
-    def _tr_begin(self, grid):
-        if not self._tracing:
-            raise RuntimeError("MultiGrid(...) is constructed inside _gen_grid")
-        self._tr_grid = grid
-        self._tr_sym = []
-        self._tr_ops = []
-        self._tr_late = {}          # index into _tr_ops -> the symbolic form of a static edit recorded as op(s)
-        self._tr_draws = []         # per `_rand_int` so far: the (lowest, highest) value it can take, over all earlier draws
-        self._tr_guard = 0          # the guard bits (MG_GEN_GUARD) of the branch being recorded: ORed into every op's `obj`
-        self._tr_fork_i = 0         # forks met so far in this run of `_gen_grid` (an index into _tr_path)
-        self._tr_params = {}        # `_param` names of this run: name -> (register, low, high)
-
-    def _tr_static(self, sym, key, rects):
-        """A static layout edit of `_gen_grid` (grid.set / put_obj / the wall helpers).  Before the first random
-        place_obj it goes into the template (returns True: the caller writes the template); AFTER one — upstream's
-        `_gen_grid` is free Python, envs/cluttered.py:25-36 could as well put its goal last — it is recorded in the
-        ordered program as fill ops (max_tries 0: write `key` into every cell of a rectangle, replacing what a
-        placement put there, base.py:655-662) and replayed per env between the placements (returns False)."""
-        if not self._tr_ops:
-            self._tr_sym.extend(sym if isinstance(sym, list) else [sym])
-            return True
-        first = None                # the op this edit's first rectangle went into: where its symbolic form is listed
-        for (x0, y0, x1, y1) in rects:
-            # a fill that continues the one before it (same object, same rows or columns, adjacent) is the same op, larger
-            last = self._tr_ops[-1]
-            merged = None
-            if last[2] == 0 and last[0] == int(key) | self._tr_guard and last[7] is None and not any(v & N.GEN_SYM for v in last[3:7]):
-                lx0, ly0, lx1, ly1 = last[3:7]
-                if (ly0, ly1) == (y0, y1) and (lx1 == x0 or x1 == lx0):
-                    merged = (last[0], 1, 0, min(lx0, x0), y0, max(lx1, x1), y1, None)
-                elif (lx0, lx1) == (x0, x1) and (ly1 == y0 or y1 == ly0):
-                    merged = (last[0], 1, 0, x0, min(ly0, y0), x1, max(ly1, y1), None)
-            if merged is not None:
-                self._tr_ops[-1] = merged
-            else:
-                self._tr_ops.append((int(key) | self._tr_guard, 1, 0, x0, y0, x1, y1, None))
-            if first is None:
-                first = len(self._tr_ops) - 1
-        if first is not None:
-            self._tr_late.setdefault(first, []).extend(sym if isinstance(sym, list) else [sym])
-        return False
-
-    def _tr_cases(self, *operands):
-        """every value the operands (ints or GenDraw) can take together, over the static intervals of the draws in them"""
-        import itertools
-        regs = sorted({v.reg for v in operands if isinstance(v, GenDraw)})
-        spans = [range(self._tr_draws[r][0], self._tr_draws[r][1] + 1) for r in regs]
-        for vals in itertools.product(*spans):
-            d = dict(zip(regs, vals))
-            yield tuple(v.const + v.sign * d[v.reg] if isinstance(v, GenDraw) else int(v) for v in operands)
-
     def _rand_int(self, low, high):
         """gym-minigrid's `_rand_int`: `self.np_random.randint(low, high)`.  Inside `_gen_grid` the draw is recorded — every
         env makes it for itself on the device at every reset, from its own RNG, where upstream makes it — and what comes
@@ -1242,26 +1117,7 @@ class MultiGridEnv(object):
         `top` / `size`, and as a bound of a later `_rand_int`.  Programs whose every possible draw cannot be shown to stay
         legal (hi > lo here, fills inside the grid, sampling rectangles non-empty) are refused with ValueError when they
         are recorded; upstream would fail for some seeds only."""
-        if not self._tracing or self._tr_grid is None:
-            raise NotImplementedError(_NO_BRANCH % "_rand_int outside _gen_grid, or before self.grid = MultiGrid(...)")
-        for v in (low, high):
-            if not isinstance(v, GenDraw):
-                GenDraw._int(v, "_rand_int(%s)" % type(v).__name__)
-        if len(self._tr_draws) >= N.GEN_DRAWS:
-            raise NotImplementedError("_gen_grid makes more than %d _rand_int draws: a reset program holds at most %d (MG_GEN_DRAWS: "
-                                      "the draws of a reset live in one 64-bit register)" % (N.GEN_DRAWS, N.GEN_DRAWS))
-        cases = list(self._tr_cases(low, high))
-        if any(hi <= lo for lo, hi in cases):
-            raise ValueError("_rand_int(%r, %r): not high > low for every value the earlier draws can take" % (low, high))
-        vmin, vmax = min(lo for lo, _ in cases), max(hi for _, hi in cases) - 1
-        if vmin < 0 or vmax > 255:
-            raise ValueError("_rand_int(%r, %r) inside _gen_grid: values %d..%d do not fit a grid coordinate (0..255)"
-                             % (low, high, vmin, vmax))
-        reg = len(self._tr_draws)
-        self._tr_draws.append((vmin, vmax))
-        self._tr_ops.append((reg | self._tr_guard, 1, -1, _gen_enc(low), 0, _gen_enc(high), 0, None))
-        self._tr_late[len(self._tr_ops) - 1] = [("draw", reg, _gen_enc(low), _gen_enc(high))]
-        return GenDraw(reg)
+        return self._gen.rand_int(low, high)
 
     # ---- per-env parameters: a register whose value comes from device memory, not from the RNG ----------------------
     def _param(self, name, low, high, default=None):
@@ -1271,29 +1127,7 @@ class MultiGridEnv(object):
         byte table on the device (`env.params[name]`, `set_params`) when it resets, and no RNG word is consumed.  The
         recorder's proofs run over the whole interval and the device clamps what it loads to it.  One draw register and
         one table column per distinct name; naming a parameter again in the same `_gen_grid` returns the same register."""
-        if not self._tracing or self._tr_grid is None:
-            raise NotImplementedError(_NO_BRANCH % "_param outside _gen_grid, or before self.grid = MultiGrid(...)")
-        low, high = GenDraw._int(low, "_param(low=%s)" % type(low).__name__), GenDraw._int(high, "_param(high=%s)" % type(high).__name__)
-        if not 0 <= low < high <= 256:
-            raise ValueError("_param(%r, %d, %d): the interval [low, high) must be non-empty and within 0..255" % (name, low, high))
-        default = low if default is None else GenDraw._int(default, "_param(default=%s)" % type(default).__name__)
-        if not low <= default < high:
-            raise ValueError("_param(%r, %d, %d, default=%d): the default lies outside the interval" % (name, low, high, default))
-        seen = self._tr_params.get(name)
-        if seen is not None:
-            if seen[1:] != (low, high):
-                raise ValueError("_param(%r, %d, %d): declared as [%d, %d) earlier in this _gen_grid" % ((name, low, high) + seen[1:]))
-            return GenDraw(seen[0])
-        if len(self._tr_draws) >= N.GEN_DRAWS:
-            raise NotImplementedError("_gen_grid needs more than %d draw registers (MG_GEN_DRAWS): parameters share them with the "
-                                      "_rand_int draws and the copies that forks inside a branch take" % N.GEN_DRAWS)
-        col = self._param_column(name, low, high, default)
-        reg = len(self._tr_draws)
-        self._tr_draws.append((low, high - 1))
-        self._tr_params[name] = (reg, low, high)
-        self._tr_ops.append((reg | self._tr_guard, 1, N.GEN_PARAM, low, col, high, 0, None))
-        self._tr_late[len(self._tr_ops) - 1] = [("param", reg, col, low, high)]
-        return GenDraw(reg)
+        return self._gen.param(name, low, high, default)
 
     def _param_column(self, name, low, high, default):
         """the table column of parameter `name`: its own from the first time `_gen_grid` names it on, filled with `default`
@@ -1331,7 +1165,7 @@ class MultiGridEnv(object):
     def _ensure_recorded(self):
         """the recording that follows the constructor (a subclass stores its settings after the base constructor's reset)"""
         if getattr(self, "_retrace", False):
-            template, ops = self._trace_gen_grid()
+            template, ops = self._record_gen_grid()
             if self._dry:
                 self._dry_trace = (template, ops)
             else:
@@ -1585,56 +1419,7 @@ class MultiGridEnv(object):
             return int(d)
         if not isinstance(d, GenDraw):
             raise TypeError("_fork takes an int or a value of self._rand_int(...), not %s" % type(d).__name__)
-        if not self._tracing or self._tr_grid is None:
-            raise NotImplementedError(_NO_BRANCH % "_fork outside _gen_grid")
-        r = d.reg
-        lo, hi = self._tr_draws[r]
-        if lo == hi:                # decided on this path already (a one-value range, or forked before): nothing to guard
-            return d.const + d.sign * lo
-        if hi - lo + 1 > 16:
-            raise NotImplementedError("_gen_grid: a fork over more than 16 values (draw[%d] takes %d..%d here): every value is a "
-                                      "recorded path of its own" % (r, lo, hi))
-        i = self._tr_fork_i
-        self._tr_fork_i += 1
-        if i == len(self._tr_path):             # met for the first time: take its first value; the later ones are later runs
-            q = None
-            if self._tr_guard:
-                q = len(self._tr_draws)         # a branch inside a branch: the conjunction through a spare register
-                if q >= N.GEN_DRAWS:
-                    raise NotImplementedError("_gen_grid needs more than %d draw registers (MG_GEN_DRAWS) on one path: %d "
-                                              "_rand_int draws and the copies that forks inside a branch of another draw take"
-                                              % (N.GEN_DRAWS, N.GEN_DRAWS))
-                if hi + 1 > 255:
-                    raise NotImplementedError("_gen_grid: a fork inside a branch of another draw, on a draw that may be 255: its "
-                                              "copy `draw + 1` must fit a byte of the draw registers")
-            self._tr_path.append(dict(values=list(range(lo, hi + 1)), idx=0, q=q, zero=q in self._tr_written))
-        f = self._tr_path[i]
-        if f["values"] != list(range(lo, hi + 1)):
-            raise ValueError("_gen_grid is not a function of its arguments and its draws: run again for another path it forked "
-                             "over other values")
-        v = f["values"][f["idx"]]
-        self._tr_draws[r] = (v, v)              # inside the branch the draw's interval is the guard's: every later proof is per path
-        if f["q"] is None:
-            self._tr_guard = self._guard_bits(r, v, v)
-        else:
-            # under the outer guard: q = draw[r] + 1, a one-value DRAW (no RNG word).  Registers start every reset at 0 — a
-            # number that a branch recorded earlier may have written is zeroed first, in every env —, so q == v + 1 says
-            # "the outer branch was taken and draw[r] == v"
-            q = f["q"]
-            src = GenDraw(r)
-            if f["zero"]:
-                self._tr_ops.append((q, 1, -1, 0, 0, 1, 0, None))
-                self._tr_late[len(self._tr_ops) - 1] = [("draw", q, 0, 1)]
-            self._tr_ops.append((q | self._tr_guard, 1, -1, (src + 1).encode(), 0, (src + 2).encode(), 0, None))
-            self._tr_late[len(self._tr_ops) - 1] = [("draw", q, (src + 1).encode(), (src + 2).encode())]
-            self._tr_draws.append((v + 1, v + 1))
-            self._tr_guard = self._guard_bits(q, v + 1, v + 1)
-        f["start"] = len(self._tr_ops)          # the branch's own ops begin here
-        return d.const + d.sign * v
-
-    @staticmethod
-    def _guard_bits(r, lo, hi):
-        return N.GEN_GUARD | (r << N.GEN_GUARD_DRAW_SHIFT) | (hi << N.GEN_GUARD_HI_SHIFT) | (lo << N.GEN_GUARD_LO_SHIFT)
+        return self._gen.fork(d)
 
     def _rand_elem(self, iterable):
         """gym-minigrid's `_rand_elem`: one element of `iterable`, by a `_rand_int(0, len)` draw.  Inside `_gen_grid` the draw
@@ -1646,118 +1431,18 @@ class MultiGridEnv(object):
         """gym-minigrid's `_rand_bool`: `self.np_random.randint(0, 2) == 0` — a draw of (0, 2) and a fork on it"""
         return self._fork(self._rand_int(0, 2)) == 0
 
-    def _tr_fill_sym(self, key, rects):
-        """A static edit with a draw among its coordinates: one fill op per rectangle, its operands evaluated per env on the
-        device; never merged with its neighbours.  Proved here for every possible draw: non-empty and inside the grid."""
-        g = self._tr_grid
-        for rect in rects:
-            cases = list(self._tr_cases(*rect))
-            if any(not (0 <= x0 < x1 <= self.width and 0 <= y0 < y1 <= self.height) for x0, y0, x1, y1 in cases):
-                raise ValueError("_gen_grid: the edit of cells [%r, %r) x [%r, %r) is not inside the %d x %d grid and non-empty for "
-                                 "every value the draws can take" % (rect[0], rect[2], rect[1], rect[3], self.width, self.height))
-            enc = tuple(_gen_enc(v) for v in rect)
-            self._tr_ops.append((int(key) | self._tr_guard, 1, 0) + enc + (None,))
-            self._tr_late[len(self._tr_ops) - 1] = [("fill", int(key)) + enc]
-            # every cell the edit can reach may have been written: get() there warns
-            g._maybe[min(c[0] for c in cases):max(c[2] for c in cases), min(c[1] for c in cases):max(c[3] for c in cases)] = True
-
-    def _place_region_sym(self, top, size):
-        """place_obj's sampling rectangle with a draw in `top` / `size`: constants clamped here, the rest on the device
-        (base.py:692-695); returns the operands and the hull of the rectangles the draws can produce"""
-        top = (0, 0) if top is None else tuple(top)
-        size = (self.width, self.height) if size is None else tuple(size)
-        for v in tuple(top) + tuple(size):
-            if not isinstance(v, GenDraw):
-                GenDraw._int(v, "place_obj(top=, size=) of %s" % type(v).__name__)
-        # upstream clamps `top` first and adds `size` to the CLAMPED top (base.py:692, 695): a rectangle that starts outside the
-        # grid keeps its extent.  A constant top is clamped here; a drawn one on the device, which moves the far edge with it
-        x0, y0 = (v if isinstance(v, GenDraw) else max(int(v), 0) for v in top)
-        x1, y1 = _gen_add(x0, size[0]), _gen_add(y0, size[1])
-        x1, y1 = (v if isinstance(v, GenDraw) else min(int(v), lim) for v, lim in ((x1, self.width), (y1, self.height)))
-        clamped = [(max(a, 0), max(b, 0), min(max(a, 0) + (c - a), self.width), min(max(b, 0) + (d - b), self.height))
-                   for a, b, c, d in self._tr_cases(x0, y0, x1, y1)]
-        if any(c <= a or d <= b for a, b, c, d in clamped):
-            raise ValueError("place_obj: the sampling rectangle [%r, %r) x [%r, %r) is empty for some value the draws can take"
-                             % (x0, x1, y0, y1))
-        hull = (min(c[0] for c in clamped), min(c[1] for c in clamped), max(c[2] for c in clamped), max(c[3] for c in clamped))
-        return (x0, y0, x1, y1), hull
-
-    def _trace_gen_grid(self):
-        """Record `_gen_grid`: once if it forks on no draw, else once per path (`_fork`), depth first, every run from a fresh
-        MultiGrid and recorder state; the runs merged into ONE program — the ops before a fork once, then each branch's ops
-        under its guard, recursively (a path's ops are contiguous from its last fork on: no branch rejoins)."""
-        self._tr_path = []          # the forks of the path being recorded: dict(values, idx, q, zero, start)
-        self._tr_written = set()    # draw registers that the branches recorded so far write
-        merged = sym = late = template = grid = spawn = None
-        runs = 0
-        while True:
-            runs += 1
-            if runs > 64:
-                raise NotImplementedError("_gen_grid forks into more than 64 paths: every path is recorded by a run of its own and "
-                                          "every env replays the whole merged program")
-            self._tracing = True
-            self._tr_grid = None
-            _trace.env = self
-            try:
-                self._gen_grid(self.width, self.height)
-            finally:
-                _trace.env = None
-                self._tracing = False
-            g = self._tr_grid
-            if g is None or self.grid is not g:
-                raise RuntimeError("_gen_grid must assign self.grid = MultiGrid((width, height))")
-            kw = self.agent_spawn_kwargs or {}
-            if _any_draw(*[v for k in ("top", "size") if kw.get(k) is not None for v in kw[k]]):
-                raise NotImplementedError("agent_spawn_kwargs with a _rand_int draw: the spawn rectangle is also used by respawn and "
-                                          "late spawns, long after the reset that made the draw — not supported")
-            if self._tr_fork_i != len(self._tr_path):
-                raise ValueError("_gen_grid is not a function of its arguments and its draws: run again for another path it made "
-                                 "fewer forks")
-            if merged is None:
-                merged, sym, late, template = list(self._tr_ops), list(self._tr_sym), dict(self._tr_late), g._template
-                grid, spawn = g, self.agent_spawn_kwargs
-            else:
-                # the run shares everything before the fork whose next value it took with the runs before it
-                if (self._tr_ops[:shared] != prefix or self._tr_sym != sym or not np.array_equal(g._template, template)):
-                    raise ValueError("_gen_grid is not a function of its arguments and its draws: run again for another path it "
-                                     "recorded another layout before the fork")
-                if not _same_spawn(self.agent_spawn_kwargs, spawn):
-                    raise ValueError("_gen_grid leaves agent_spawn_kwargs that differ between the paths of a fork: the spawn "
-                                     "rectangle is the launch's, not an env's")
-                for i, e in self._tr_late.items():
-                    if i >= shared:
-                        late[len(merged) + i - shared] = e
-                merged.extend(self._tr_ops[shared:])
-                # the grid that stays is the first run's: a cell that another path draws differently, or may have filled,
-                # counts as "may have been written" there (`grid.get()` warns on it, whatever path is asked about)
-                grid._maybe |= g._maybe | (g._shadow != grid._shadow)
-            self._tr_written.update(op[0] & (N.GEN_DRAWS - 1) for op in self._tr_ops if op[2] < 0)
-            while self._tr_path and self._tr_path[-1]["idx"] + 1 == len(self._tr_path[-1]["values"]):
-                self._tr_path.pop()
-            if not self._tr_path:
-                break
-            self._tr_path[-1]["idx"] += 1       # the next path: the deepest fork with a value left takes it
-            shared = self._tr_path[-1]["start"]
-            prefix = self._tr_ops[:shared]
-        self.grid = self._tr_grid = grid        # (the first run's: the template is the same in every run, `_maybe` covers them all)
-        if len(merged) > N.MAX_GEN:
-            fills = sum(1 for op in merged if op[2] == 0)
-            raise NotImplementedError("_gen_grid records %d reset-program ops — %d groups of random placements and %d rectangle "
-                                      "fills for static edits made after the first place_obj — and a device program holds at most "
-                                      "%d (MG_MAX_GEN: a sanity bound — every env replays the whole program at every reset): draw the "
-                                      "static layout before the first place_obj (it then costs nothing)"
-                                      % (len(merged), len(merged) - fills, fills, N.MAX_GEN))
-        self._tr_ops, self._tr_late = merged, late
-        self._spec_last = dict(sym=list(sym), ops=list(merged), late=dict(late))
-        return template, list(merged)
+    def _record_gen_grid(self):
+        """run `_gen_grid` under the recorder (gen_recorder.GenRecorder.record): the template and the reset program's ops"""
+        self._spec_last = rec = self._gen.record()
+        return rec.template, list(rec.ops)
 
     @_on_device
     def put_obj(self, obj, i, j, env_mask=None):
         """Put an object at a specific position, replacing what is there (base.py:655-662) — an agent standing
         there included: as upstream it is in no cell afterwards (nobody sees it; it keeps its position, turns
         and looks), and its next successful forward move raises what upstream raises (MG_AF_EVICTED)."""
-        if self._tracing:
-            self._tr_grid.set(i, j, obj)
+        if self._gen.active:
+            self._gen.grid.set(i, j, obj)
             return True
         assert 0 <= i < self.width and 0 <= j < self.height
         key = self.obj_reg.get_key(obj)
@@ -1776,13 +1461,13 @@ class MultiGridEnv(object):
 
     def _place_region(self, top, size):
         # sampling rectangle, clamped exactly like base.py:692-695
-        top = (0, 0) if top is None else (max(int(top[0]), 0), max(int(top[1]), 0))
-        if size is None:
-            size = (self.width, self.height)
-        x1, y1 = min(top[0] + int(size[0]), self.width), min(top[1] + int(size[1]), self.height)
-        if x1 <= top[0] or y1 <= top[1]:
+        x0, y0 = (0, 0) if top is None else top[:2]
+        w, h = (self.width, self.height) if size is None else size[:2]
+        x0, y0 = max(int(x0), 0), max(int(y0), 0)
+        x1, y1 = min(x0 + int(w), self.width), min(y0 + int(h), self.height)
+        if x1 <= x0 or y1 <= y0:
             raise ValueError("place_obj: empty sampling rectangle")
-        return top[0], top[1], x1, y1
+        return x0, y0, x1, y1
 
     def _what(self, obj):
         if isinstance(obj, GridAgentInterface):
@@ -1829,50 +1514,18 @@ class MultiGridEnv(object):
         sampling rectangle once (see `_reject_table`).  `count` (not upstream's; inside `_gen_grid` only): that many
         placements in a row — an int is the same as so many calls, a `_rand_int` / `_param` value is a count that every env
         evaluates for itself at its reset (never below 0, proved when recorded)."""
-        if not self._tracing:
+        if not self._gen.active:
             if isinstance(count, GenDraw) or count != 1:
                 raise NotImplementedError("place_obj(count=) is for the recorded placements of _gen_grid")
             return self._place_live(obj, top, size, max_tries, env_mask, reject_fn)
-        if isinstance(count, GenDraw):
-            if any(c < 0 for c, in self._tr_cases(count)):
-                raise ValueError("place_obj(count=%r): below 0 for some value the draws can take" % (count,))
-            n_rec = count.encode()
-        else:
-            n_rec = GenDraw._int(count, "place_obj(count=%s)" % type(count).__name__)
-            if n_rec < 0:
-                raise ValueError("place_obj(count=%d): a count is not negative" % n_rec)
-            if n_rec == 0:
-                return None
-        if isinstance(obj, GridAgentInterface):
-            raise NotImplementedError("inside _gen_grid agents are placed by reset() itself")
-        max_tries = int(max(1, min(max_tries, 1e5)))
-        key = self.obj_reg.get_key(obj)
-        if _any_draw(*[v for r in (top, size) if r is not None for v in r]):
-            operands, region = self._place_region_sym(top, size)    # (region: the hull — every cell some draw can sample)
-            operands = tuple(_gen_enc(v) for v in operands)
-        else:
-            operands = region = self._place_region(top, size)
-        rej = self._reject_table(reject_fn, region)
-        key |= self._tr_guard
-        op = (key, n_rec, max_tries) + operands + (None if rej is None else rej.tobytes(),)
-        x0, y0, x1, y1 = region
-        may = self._tr_grid._shadow[x0:x1, y0:y1] == 0          # (only empty cells accept a placement, base.py:672-679)
-        if rej is not None:
-            may &= rej[x0:x1, y0:y1] == 0
-        self._tr_grid._maybe[x0:x1, y0:y1] |= may
-        if (self._tr_ops and self._tr_ops[-1][0] == key and self._tr_ops[-1][2:] == op[2:] and self._tr_ops[-1][2] > 0
-                and not (self._tr_ops[-1][1] | n_rec) & N.GEN_SYM):      # (a symbolic count is an op of its own)
-            self._tr_ops[-1] = (key, self._tr_ops[-1][1] + n_rec) + op[2:]
-        else:
-            self._tr_ops.append(op)
-        return None
+        return self._gen.place_obj(obj, top, size, reject_fn, max_tries, count)
 
     @_on_device
     def try_place_obj(self, obj, pos, env_mask=None):
         """Try to place `obj` (an object, or one of this env's agents) at `pos` — one (x, y) for every
         env or a (B, 2) tensor — and return a (B,) bool tensor saying where it worked (base.py:664-688)."""
         import torch
-        if self._tracing:
+        if self._gen.active:
             raise NotImplementedError("inside _gen_grid use put_obj / place_obj")
         what = self._what(obj)
         self._sync_tables()
@@ -2105,7 +1758,7 @@ class MultiGridEnv(object):
         key = (template.tobytes(), tuple(ops))
         # a program with a PARAM op reads the env's parameter table right behind its template: all such programs of this env
         # share ONE buffer — template, then table —, whose head is rewritten (in stream order) when the template changes
-        has_param = any(op[2] == N.GEN_PARAM for op in ops)
+        has_param = any(op.is_param for op in ops)
         if has_param and self._param_tpl != key[0]:
             t = np.zeros(self.cells_stride, np.uint8)
             t[:self.width * self.height] = template.reshape(-1)
@@ -2125,35 +1778,13 @@ class MultiGridEnv(object):
             prog._template_dev = torch.from_numpy(t).to(self.device)
         prog.template_grid = prog._template_dev.data_ptr()
         prog.n_ops = len(ops)
-        tables = []                   # place_obj(reject_fn=) tables, one row of cells_stride bytes each
-        host_ops = (N.GenOp * max(1, len(ops)))()
-        for i, (obj, count, max_tries, x0, y0, x1, y1, rej) in enumerate(ops):
-            # (the library cannot look into device memory from the host: what the kernels rely on is checked here)
-            # the guard of a branch in the upper bits of obj (MG_GEN_GUARD): lo <= hi; the low byte as ever
-            guard, low = obj & ~0xFF, obj & 0xFF
-            assert guard == 0 or (guard & ~0x07FFFF00 == N.GEN_GUARD
-                                  and (guard >> N.GEN_GUARD_LO_SHIFT) & 0xFF <= (guard >> N.GEN_GUARD_HI_SHIFT) & 0xFF)
-            if max_tries < 0:       # a `_rand_int` draw, or a PARAM load: obj is its register, y0 a PARAM's table column
-                assert 0 <= low < N.GEN_DRAWS and max_tries in (-1, N.GEN_PARAM)
-                assert max_tries == -1 or (0 <= y0 < N.GEN_DRAWS and 0 <= x0 < x1 <= 256)
-            else:
-                assert (1 if max_tries > 0 else 0) <= low < len(self.obj_reg.objs) and count >= 0
-                # (a rectangle with a draw operand was proved by the recorder and is clamped on the device)
-                assert any(v & N.GEN_SYM for v in (x0, y0, x1, y1)) or (0 <= x0 < x1 <= self.width and 0 <= y0 < y1 <= self.height)
-            o = host_ops[i]
-            o.obj, o.count, o.max_tries, o.x0, o.y0, o.x1, o.y1 = obj, count, max_tries, x0, y0, x1, y1
-            o.reject = -1
-            if rej is not None:
-                row = np.zeros(self.cells_stride, np.uint8)
-                row[:self.width * self.height] = np.frombuffer(rej, np.uint8)
-                o.reject = len(tables)
-                tables.append(row)
+        host_ops, reject = pack_program(ops, self.width, self.height, self.cells_stride, len(self.obj_reg.objs))
         # the ops live in device memory (MgGenProgram::ops), kept alive on the struct like the template
         prog._ops_dev = torch.from_numpy(np.frombuffer(bytes(host_ops), np.uint8).copy()).to(self.device)
         prog.ops = prog._ops_dev.data_ptr()
-        prog.n_reject = len(tables)
-        if tables:
-            prog._reject_dev = torch.from_numpy(np.stack(tables)).to(self.device)
+        prog.n_reject = 0 if reject is None else len(reject)
+        if reject is not None:
+            prog._reject_dev = torch.from_numpy(reject).to(self.device)
             prog.reject = prog._reject_dev.data_ptr()
         self._prog_cache[key] = prog
         return prog
@@ -2173,7 +1804,7 @@ class MultiGridEnv(object):
     def reset(self, env_mask=None, **kwargs):
         """Start a new episode in every env (or those selected by `env_mask`) and return the
         observation tensor (B, n, P, P, 3) — base.py:402-416."""
-        template, ops = self._trace_gen_grid()
+        template, ops = self._record_gen_grid()
         if self._dry:
             self._dry_trace = (template, ops)     # host-only instance: the recorded layout, nothing runs
             return None
@@ -2688,36 +2319,7 @@ class MultiGridEnv(object):
                          initial_reward=o.initial_reward, reset_on_mistake=o.reset_on_mistake)
             return d
 
-        def prog(p):
-            out = list(p["sym"])
-            late = p.get("late", {})
-            for i, (k, c, t, x0, y0, x1, y1, rej) in enumerate(p["ops"]):
-                if k & N.GEN_GUARD and k & ~0xFF:
-                    # an op of a branch on a draw: ("guard", r, lo, hi, entry) — the entry as below, run only where
-                    # lo <= draw[r] <= hi (no oracle replays these)
-                    grd = ("guard", (k >> N.GEN_GUARD_DRAW_SHIFT) & 7, (k >> N.GEN_GUARD_LO_SHIFT) & 0xFF,
-                           (k >> N.GEN_GUARD_HI_SHIFT) & 0xFF)
-                    if t <= 0:
-                        out.extend(grd + (e,) for e in late.get(i, []))
-                    else:
-                        entry = ("place_sym", k & 0xFF, c, t, x0, y0, x1, y1)
-                        if rej is not None:
-                            cells = np.argwhere(np.frombuffer(rej, np.uint8).reshape(self.width, self.height))
-                            entry += (tuple((int(x), int(y)) for x, y in cells),)
-                        out.append(grd + (entry,))
-                    continue
-                if t <= 0:               # a static edit after a placement, or a draw: its symbolic form, once
-                    out.extend(late.get(i, []))
-                    continue
-                full = (x0, y0, x1, y1) == (0, 0, self.width, self.height)
-                if any(v & N.GEN_SYM for v in (x0, y0, x1, y1)):      # (encoded operands: no oracle replays these)
-                    out.append(("place_sym", k, c, t, x0, y0, x1, y1))
-                elif rej is not None:      # reject_fn, tabulated: the rejected cells of the sampling rectangle
-                    cells = np.argwhere(np.frombuffer(rej, np.uint8).reshape(self.width, self.height))
-                    out.append(("place", k, c, t, x0, y0, x1, y1, tuple((int(x), int(y)) for x, y in cells)))
-                else:
-                    out.append(("place", k, c, t) if full else ("place", k, c, t, x0, y0, x1, y1))
-            return out
+
         def aspec(a):
             d = dict(color=a.color)
             if a.spawn_delay:
@@ -2746,8 +2348,8 @@ class MultiGridEnv(object):
                     see_through_walls=self.see_through_walls, max_steps=self.max_steps,
                     reward_decay=bool(self.reward_decay), ghost_mode=self.ghost_mode,
                     respawn=bool(self.respawn), objects=[ospec(o) for o in self.obj_reg.objs],
-                    wall_obj=self.obj_reg.find(Wall()), gen_ctor=prog(self._spec_ctor or self._spec_last),
-                    gen_reset=prog(self._spec_last))
+                    wall_obj=self.obj_reg.find(Wall()), gen_ctor=decode_program(self._spec_ctor or self._spec_last, self.width, self.height),
+                    gen_reset=decode_program(self._spec_last, self.width, self.height))
 
     @_on_device
     def render(self, mode="rgb_array", close=False, highlight=True, tile_size=TILE_PIXELS, show_agent_views=True,

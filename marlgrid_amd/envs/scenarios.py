@@ -4,7 +4,7 @@ Each class describes a layout through `_gen_grid`, written against the same `Mul
 `put_obj` / `place_obj` vocabulary as upstream's `marlgrid/envs/{empty,cluttered,goalcycle,
 viz_test,doorkey}.py`.  Here `_gen_grid` does not build a grid: it is *recorded* (static cells -> a template,
 `place_obj` calls -> an ordered rejection-sampling program) and the HIP reset kernel replays the
-recording for every env of the batch with that env's own RNG (see `MultiGridEnv._trace_gen_grid`).
+recording for every env of the batch with that env's own RNG (see `marlgrid_amd/gen_recorder.py`).
 
 Behaviour kept from upstream on purpose: the base constructor resets once before a subclass has
 stored its own parameters, so layout parameters are read with `getattr(self, name, default)` and

@@ -15,6 +15,7 @@ import numpy as np
 
 from marlgrid_amd import _native as N
 from marlgrid_amd import seeding
+from marlgrid_amd.gen_recorder import pack_program       # the product's own packing, with its range asserts
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
@@ -92,21 +93,10 @@ class HostEmu(object):
         prog._keep = t
         prog.template_grid = t.ctypes.data
         prog.n_ops = len(ops)
-        tables = []
-        prog._keep_ops = host_ops = (N.GenOp * max(1, len(ops)))()      # ("device" memory is host memory here)
-        prog.ops = C.cast(host_ops, C.c_void_p).value
-        for i, (obj, count, max_tries, x0, y0, x1, y1, rej) in enumerate(ops):
-            o = host_ops[i]
-            o.obj, o.count, o.max_tries, o.x0, o.y0, o.x1, o.y1 = obj, count, max_tries, x0, y0, x1, y1
-            o.reject = -1
-            if rej is not None:                          # place_obj(reject_fn=), tabulated (base.py:_reject_table)
-                row = np.zeros(env.cells_stride, np.uint8)
-                row[:env.width * env.height] = np.frombuffer(rej, np.uint8)
-                o.reject = len(tables)
-                tables.append(row)
-        prog.n_reject = len(tables)
-        if tables:
-            prog._keep_reject = np.stack(tables)
+        prog._keep_ops, prog._keep_reject = pack_program(ops, env.width, env.height, env.cells_stride, len(env.obj_reg.objs))
+        prog.ops = C.cast(prog._keep_ops, C.c_void_p).value     # ("device" memory is host memory here)
+        prog.n_reject = 0 if prog._keep_reject is None else len(prog._keep_reject)
+        if prog._keep_reject is not None:
             prog.reject = prog._keep_reject.ctypes.data
         return prog
 

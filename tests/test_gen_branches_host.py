@@ -319,7 +319,7 @@ def test_grid_get_warns_on_cells_that_any_path_may_have_written():
             self.put_obj(Wall(), 3, 3)
             self.place_obj(Wall(), top=(5, 1), size=(1, 3), max_tries=10)
     env, _ = _record(gen)
-    env._tracing = True
+    env._gen.active = True
     try:
         with warnings.catch_warnings(record=True) as w:
             warnings.simplefilter("always")
@@ -329,7 +329,7 @@ def test_grid_get_warns_on_cells_that_any_path_may_have_written():
             env.grid.get(5, 2)
             assert len(w) == 2 and "may have filled" in str(w[0].message)
     finally:
-        env._tracing = False
+        env._gen.active = False
 
 
 def test_bound_more_than_max_gen_ops():

@@ -186,7 +186,7 @@ def test_split_program_operands_and_bookkeeping():
         (1, 2, 100, 0, 0, S, 7, None),                       # the two clutter walls: one op, count 2
     ]
     g = env.grid
-    env._tracing = True                                      # (get() as `_gen_grid` sees it)
+    env._gen.active = True                                   # (get() as `_gen_grid` sees it)
     try:
         with warnings.catch_warnings(record=True) as w:
             warnings.simplefilter("always")
@@ -196,7 +196,7 @@ def test_split_program_operands_and_bookkeeping():
             g.get(5, 3)                                      # right of every possible column: only the goal's placement reaches it
             assert len(w) == 2
     finally:
-        env._tracing = False
+        env._gen.active = False
 
 
 def test_place_obj_clamps_the_top_first_and_adds_the_size_to_the_clamped_top():

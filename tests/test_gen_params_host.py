@@ -292,7 +292,7 @@ def test_cluttered_curriculum_id_and_the_untouched_class():
     assert env.params["n_clutter"].tolist() == [25, 25, 25]
     wall = env.obj_reg.find(Wall())
     goal = env.obj_reg.find(Goal(color="green", reward=1))
-    assert env._spec_ctor["ops"] == [(goal, 1, 100, 0, 0, 15, 15, None)]    # the constructor's reset: no clutter, as ever
+    assert env._spec_ctor.ops == [(goal, 1, 100, 0, 0, 15, 15, None)]    # the constructor's reset: no clutter, as ever
     assert env._dry_trace[1] == [(0, 1, N.GEN_PARAM, 0, 0, 51, 0, None), (wall, N.GEN_SYM, 100, 0, 0, 15, 15, None)]
     # without the kwarg: the class as it was — no parameter, no table, the same program as before
     plain = E.make("MarlGrid-3AgentCluttered15x15-v0", batch_size=3, _dry=True)

@@ -113,6 +113,8 @@ struct MgoEnv {
     int32_t step_count;
     int draw[MGO_MAX_DRAWS];                           /* the `_rand_int` values of the running / last `_gen_grid` */
     int draw_words[MGO_MAX_DRAWS];                     /* RNG words each consumed; -1: not drawn */
+    int param[MGO_MAX_PARAMS];                         /* the env's `_gen_grid` parameters (PARAM) */
+    int8_t cond[MGO_MAX_GEN];                          /* the IFs of the last `_gen_grid`: 1 / 0, -1 not evaluated */
     uint32_t mt[MT_N];
     int32_t mt_pos;
 };
@@ -301,6 +303,7 @@ static MgoEnv* env_alloc(MgoShared* sh, const uint32_t* key, int32_t key_len) {
     e->cell_agents = (int32_t*)calloc((size_t)nc * MGO_MAX_AGENTS, sizeof(int32_t));
     e->cell_nagents = (int32_t*)calloc(nc, sizeof(int32_t));
     for (int k = 0; k < MGO_MAX_AGENTS; k++) { e->ax[k] = e->ay[k] = -1; e->abonus[k] = -1; }
+    for (int p = 0; p < MGO_MAX_PARAMS; p++) e->param[p] = sh->cfg.param_default[p];
     /* MultiGridEnv.seed — base.py:371-374 */
     mgo_mt_init_by_array(e->mt, &e->mt_pos, key, key_len);
     return e;
@@ -406,18 +409,59 @@ static int operand(const MgoEnv* e, const MgoOperand* o) {
     return o->reg < 0 ? o->c : o->c + o->sign * e->draw[o->reg];
 }
 
+/* the object of a PUT / FILL / PLACE / PLACE_SYM: `obj`, or `lst[i]` of a `_rand_elem` over objects (-1: IndexError) */
+static int gen_object(const MgoEnv* e, const MgoGenOp* op) {
+    if (op->sel_reg < 0) return op->obj;
+    int i = e->draw[op->sel_reg];
+    if (i < 0) i += op->n_sel;                       /* Python's lst[-1] */
+    return (i < 0 || i >= op->n_sel) ? -1 : op->sel[i];
+}
+
+/* the index of the op behind the block that begins after op `g` (an IF or an ELSE): its ELSE (when `to_else`) or its ENDIF,
+ * nested blocks walked over; n when the program ends first */
+static int gen_block_end(const MgoGenOp* ops, int n, int g, int to_else) {
+    int depth = 0;
+    for (g++; g < n; g++) {
+        if (ops[g].kind == MGO_GEN_IF) depth++;
+        else if (ops[g].kind == MGO_GEN_ENDIF) { if (depth == 0) return g; depth--; }
+        else if (ops[g].kind == MGO_GEN_ELSE && depth == 0 && to_else) return g;
+    }
+    return n;
+}
+
 /* `_gen_grid`: envs/empty.py:9-16, envs/cluttered.py:25-36, envs/goalcycle.py:30-51,
  * envs/viz_test.py:9-15, envs/doorkey.py:15-41 (`_rand_int`: gym-minigrid's np_random.randint(low, high)), the scenarios of
- * tests/draw_envs.py; wall helpers base.py:160-176 */
+ * tests/draw_envs.py, tests/gen_branch_envs.py (`if` on a draw, `_rand_elem`, `_rand_bool`) and tests/param_envs.py; wall helpers base.py:160-176 */
 static int gen_grid(MgoEnv* e, int which) {
     const MgoConfig* cfg = &e->sh->cfg;
     int nc = cfg->W * cfg->H;
     for (int r = 0; r < MGO_MAX_DRAWS; r++) { e->draw[r] = 0; e->draw_words[r] = -1; }
+    memset(e->cond, -1, sizeof(e->cond));
     memset(e->cell, 0, nc * sizeof(int32_t));          /* MultiGrid((W,H)) — base.py:87-101 */
     memset(e->cell_nagents, 0, nc * sizeof(int32_t));
-    for (int g = 0; g < cfg->n_gen[which]; g++) {
-        const MgoGenOp* op = &cfg->gen[which][g];
+    const MgoGenOp* ops = cfg->gen[which];
+    const int n_ops = cfg->n_gen[which];
+    for (int g = 0; g < n_ops; g++) {
+        const MgoGenOp* op = &ops[g];
         switch (op->kind) {
+        case MGO_GEN_IF: {
+            /* `if lo <= v <= hi:` — Python runs one of the two suites and never looks at the other */
+            int v = operand(e, &op->a[0]), lo = operand(e, &op->a[1]), hi = operand(e, &op->a[2]);
+            int holds = lo <= v && v <= hi;
+            e->cond[g] = (int8_t)holds;
+            if (!holds) g = gen_block_end(ops, n_ops, g, 1);     /* on to the ELSE's suite, or past the ENDIF */
+            break;
+        }
+        case MGO_GEN_ELSE:                                       /* reached from the `if` suite that ran: skip the other */
+            g = gen_block_end(ops, n_ops, g, 0);
+            break;
+        case MGO_GEN_ENDIF:
+            break;
+        case MGO_GEN_PARAM:
+            if (op->obj < 0 || op->obj >= MGO_MAX_DRAWS || op->a[0].c < 0 || op->a[0].c >= MGO_MAX_PARAMS) return MGO_ERR_VALUE;
+            e->draw[op->obj] = e->param[op->a[0].c];
+            e->draw_words[op->obj] = 0;
+            break;
         case MGO_GEN_WALL_RECT:
             for (int i = 0; i < op->w; i++) { grid_set_wall(e, op->x + i, op->y); grid_set_wall(e, op->x + i, op->y + op->h - 1); }
             for (int j = 0; j < op->h; j++) { grid_set_wall(e, op->x, op->y + j); grid_set_wall(e, op->x + op->w - 1, op->y + j); }
@@ -428,16 +472,22 @@ static int gen_grid(MgoEnv* e, int which) {
         case MGO_GEN_VERT_WALL:
             for (int j = 0; j < op->h; j++) grid_set_wall(e, op->x, op->y + j);
             break;
-        case MGO_GEN_PUT:
-            mgo_put_obj(e, op->obj, op->x, op->y);
+        case MGO_GEN_PUT: {
+            int obj = gen_object(e, op);
+            if (obj < 0) return MGO_ERR_VALUE;
+            mgo_put_obj(e, obj, op->x, op->y);
             break;
-        case MGO_GEN_PLACE:
-            for (int n = 0; n < op->count; n++) {
-                int rc = (op->w > 0) ? place_obj_in(e, op->obj, (double)op->max_tries, op->x, op->y, op->x + op->w, op->y + op->h, op->reject, 0, 0)
-                                     : place_obj(e, op->obj, (double)op->max_tries, op->reject);
+        }
+        case MGO_GEN_PLACE: {
+            int obj = gen_object(e, op), count = operand(e, &op->cnt);
+            if (obj < 0) return MGO_ERR_VALUE;
+            for (int n = 0; n < count; n++) {
+                int rc = (op->w > 0) ? place_obj_in(e, obj, (double)op->max_tries, op->x, op->y, op->x + op->w, op->y + op->h, op->reject, 0, 0)
+                                     : place_obj(e, obj, (double)op->max_tries, op->reject);
                 if (rc != MGO_OK) return rc;
             }
             break;
+        }
         case MGO_GEN_DRAW: {
             /* v = self._rand_int(lo, hi) -> np_random.randint(lo, hi): lo + bounded(hi - lo - 1); ValueError on low >= high */
             int lo = operand(e, &op->a[0]), hi = operand(e, &op->a[1]);
@@ -451,23 +501,28 @@ static int gen_grid(MgoEnv* e, int which) {
             /* grid.set(x, y, obj) cell by cell (put_obj base.py:655-662, vert_wall / horz_wall / wall_rect base.py:160-176):
              * `assert i >= 0 and i < self.width` (base.py:149-152) — nothing is clamped */
             int x0 = operand(e, &op->a[0]), y0 = operand(e, &op->a[1]), x1 = operand(e, &op->a[2]), y1 = operand(e, &op->a[3]);
+            int obj = gen_object(e, op);
+            if (obj < 0) return MGO_ERR_VALUE;
             for (int x = x0; x < x1; x++)
                 for (int y = y0; y < y1; y++) {
-                    int rc = mgo_put_obj(e, op->obj, x, y);
+                    int rc = mgo_put_obj(e, obj, x, y);
                     if (rc != MGO_OK) return rc;
                 }
             break;
         }
         case MGO_GEN_PLACE_SYM: {
             /* place_obj(obj, top=, size=) — base.py:692-695: top = max(top, 0); bottom = min(top + size, (W, H)) with the
-             * CLAMPED top; then np_random.randint(top, bottom) per try (ValueError on an empty range) */
-            int tx = operand(e, &op->a[0]), ty = operand(e, &op->a[1]);
-            int sx = operand(e, &op->a[2]) - tx, sy = operand(e, &op->a[3]) - ty;
-            int x0 = tx > 0 ? tx : 0, y0 = ty > 0 ? ty : 0;
-            int x1 = x0 + sx < cfg->W ? x0 + sx : cfg->W, y1 = y0 + sy < cfg->H ? y0 + sy : cfg->H;
-            if (x1 <= x0 || y1 <= y0) return MGO_ERR_VALUE;
-            for (int n = 0; n < op->count; n++) {
-                int rc = place_obj_in(e, op->obj, (double)op->max_tries, x0, y0, x1, y1, op->reject, 0, 0);
+             * CLAMPED top; then np_random.randint(top, bottom) per try (ValueError on an empty range) — per call: a count
+             * below 1 makes no call */
+            int obj = gen_object(e, op), count = operand(e, &op->cnt);
+            if (obj < 0) return MGO_ERR_VALUE;
+            for (int n = 0; n < count; n++) {
+                int tx = operand(e, &op->a[0]), ty = operand(e, &op->a[1]);
+                int sx = operand(e, &op->a[2]) - tx, sy = operand(e, &op->a[3]) - ty;
+                int x0 = tx > 0 ? tx : 0, y0 = ty > 0 ? ty : 0;
+                int x1 = x0 + sx < cfg->W ? x0 + sx : cfg->W, y1 = y0 + sy < cfg->H ? y0 + sy : cfg->H;
+                if (x1 <= x0 || y1 <= y0) return MGO_ERR_VALUE;
+                int rc = place_obj_in(e, obj, (double)op->max_tries, x0, y0, x1, y1, op->reject, 0, 0);
                 if (rc != MGO_OK) return rc;
             }
             break;
@@ -957,6 +1012,10 @@ void mgo_get_mt(const MgoEnv* e, uint32_t* mt624, int32_t* pos) {
 void mgo_get_draws(const MgoEnv* e, int32_t* draws, int32_t* words) {
     for (int r = 0; r < MGO_MAX_DRAWS; r++) { draws[r] = e->draw_words[r] < 0 ? -1 : e->draw[r]; words[r] = e->draw_words[r]; }
 }
+
+void mgo_get_conds(const MgoEnv* e, int8_t* conds) { memcpy(conds, e->cond, sizeof(e->cond)); }
+void mgo_set_param(MgoEnv* e, int32_t param, int32_t value) { if (param >= 0 && param < MGO_MAX_PARAMS) e->param[param] = value; }
+int32_t mgo_get_param(const MgoEnv* e, int32_t param) { return (param >= 0 && param < MGO_MAX_PARAMS) ? e->param[param] : 0; }
 
 void mgo_set_agent_dir(MgoEnv* e, int32_t k, int32_t dir) { e->adir[k] = ((dir % 4) + 4) % 4; }
 void mgo_set_carrying(MgoEnv* e, int32_t k, int32_t obj) { e->acarry[k] = obj; }

@@ -27,7 +27,7 @@ extern "C" {
 #define MGO_MAX_AGENTS 32
 #define MGO_MAX_OBJ 256
 #define MGO_MAX_FILL 8
-#define MGO_MAX_GEN 192
+#define MGO_MAX_GEN 256
 #define MGO_MAX_VIEW 31
 #define MGO_AGENT_BASE 1000 /* cell value >= this: the cell object is agent (value - base) */
 
@@ -77,10 +77,26 @@ typedef struct {
  *   FILL       grid.set(x, y, obj or None) for every cell of [a[0], a[2]) x [a[1], a[3]) (put_obj / the wall helpers with
  *              drawn coordinates).  NOT clamped: a cell outside the grid is grid.set's AssertionError (base.py:149-152)
  *   PLACE_SYM  place_obj(obj, top=(a[0], a[1]), size=(a[2] - a[0], a[3] - a[1]), max_tries), `count` times, the rectangle
- *              clamped as base.py:692-695 does: top first, then bottom = min(clamped top + size, (W, H)) */
+ *              clamped as base.py:692-695 does: top first, then bottom = min(clamped top + size, (W, H))
+ *
+ * A `_gen_grid` that BRANCHES on what it drew (`if`, gym-minigrid's `_rand_elem` / `_rand_bool`; the scenarios of
+ * tests/gen_branch_envs.py) or reads a per-env parameter (tests/param_envs.py) is control flow as Python has it: structured
+ * blocks that the interpreter walks with a nesting depth, nothing flattened and no op marked with a condition.
+ *   IF         `if a[1] <= a[0] <= a[2]:` in plain int (a[0]: the value, an operand); the ops up to the matching ELSE /
+ *              ENDIF run when it holds, those between ELSE and ENDIF otherwise.  Nests MGO_MAX_DEPTH deep.  A block that is
+ *              not taken is walked over: no RNG word, no write, no error, draw[] as it was
+ *   ELSE, ENDIF
+ *   PARAM      draw[obj] = the env's parameter a[0].c (mgo_set_param), as it is when `_gen_grid` runs; no RNG word
+ * The object of PUT / FILL / PLACE / PLACE_SYM may be `lst[i]` of a `_rand_elem` over objects: sel_reg >= 0 makes it
+ * sel[draw[sel_reg]] (an index outside the list is Python's IndexError, reported as MGO_ERR_VALUE).  `cnt` of PLACE /
+ * PLACE_SYM is an operand: that many consecutive place_obj calls, below 1 none (`for _ in range(cnt)`). */
 enum { MGO_GEN_WALL_RECT = 0, MGO_GEN_HORZ_WALL = 1, MGO_GEN_VERT_WALL = 2, MGO_GEN_PUT = 3,
-       MGO_GEN_PLACE = 4, MGO_GEN_DRAW = 5, MGO_GEN_FILL = 6, MGO_GEN_PLACE_SYM = 7 };
+       MGO_GEN_PLACE = 4, MGO_GEN_DRAW = 5, MGO_GEN_FILL = 6, MGO_GEN_PLACE_SYM = 7,
+       MGO_GEN_IF = 8, MGO_GEN_ELSE = 9, MGO_GEN_ENDIF = 10, MGO_GEN_PARAM = 11 };
 #define MGO_MAX_DRAWS 16
+#define MGO_MAX_SEL 16
+#define MGO_MAX_DEPTH 8
+#define MGO_MAX_PARAMS 16
 typedef struct {
     int32_t c, reg, sign;    /* reg < 0: the constant c; else c + sign * draw[reg], sign +1 / -1 */
 } MgoOperand;
@@ -89,7 +105,11 @@ typedef struct {
     const uint8_t* reject;   /* place_obj(reject_fn=): the callback tabulated over the grid, index x*H + y, != 0 =
                               * rejected (base.py:700-701: a rejected draw is a spent try); NULL: none.  The
                               * caller keeps it alive. */
-    MgoOperand a[4];         /* DRAW: lo, hi (obj: the register); FILL / PLACE_SYM: x0, y0, x1, y1.  Unused by kinds 0-4 */
+    MgoOperand a[4];         /* DRAW: lo, hi (obj: the register); FILL / PLACE_SYM: x0, y0, x1, y1; IF: value, lo, hi; PARAM:
+                              * a[0].c the parameter (obj: the register).  Unused by kinds 0-4 */
+    MgoOperand cnt;          /* PLACE / PLACE_SYM: how many place_obj calls (`count` is not read) */
+    int32_t sel_reg;         /* >= 0: the object is sel[draw[sel_reg]], not `obj` */
+    int32_t n_sel, sel[MGO_MAX_SEL];
 } MgoGenOp;
 
 typedef struct {
@@ -115,6 +135,7 @@ typedef struct {
     int32_t spawn_max_tries;                                      /* agent_spawn_kwargs max_tries (<= 1e5) */
     const uint8_t* spawn_reject;                                  /* agent_spawn_kwargs reject_fn, tabulated like
                                                                    * MgoGenOp.reject; NULL: none */
+    int32_t param_default[MGO_MAX_PARAMS];                        /* what a new env's parameters hold */
 } MgoConfig;
 
 typedef struct MgoEnv MgoEnv;
@@ -152,6 +173,12 @@ void mgo_get_mt(const MgoEnv* e, uint32_t* mt624, int32_t* pos);
 /* the `_rand_int` values of the env's last `_gen_grid` run and the RNG words each of them consumed (MGO_MAX_DRAWS entries
  * each; -1: that register was not drawn) */
 void mgo_get_draws(const MgoEnv* e, int32_t* draws, int32_t* words);
+/* the IF ops of the env's last `_gen_grid` run, by index into the program that ran (MGO_MAX_GEN entries): 1 the condition
+ * held, 0 it did not, -1 the op was not evaluated (no IF, or inside a block that was not taken) */
+void mgo_get_conds(const MgoEnv* e, int8_t* conds);
+/* a per-env parameter of `_gen_grid` (PARAM reads it when the env next resets) */
+void mgo_set_param(MgoEnv* e, int32_t param, int32_t value);
+int32_t mgo_get_param(const MgoEnv* e, int32_t param);
 void mgo_set_agent_dir(MgoEnv* e, int32_t k, int32_t dir);
 void mgo_set_carrying(MgoEnv* e, int32_t k, int32_t obj);
 /* test helper: overwrite a cell with a non-agent object id (env.put_obj, base.py:655-662) */

@@ -23,7 +23,8 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmgoracle.so")
 
-MAX_AGENTS, MAX_OBJ, MAX_FILL, MAX_GEN, MAX_DRAWS = 32, 256, 8, 192, 16
+MAX_AGENTS, MAX_OBJ, MAX_FILL, MAX_GEN, MAX_DRAWS = 32, 256, 8, 256, 16
+MAX_SEL, MAX_DEPTH, MAX_PARAMS = 16, 8, 16
 
 # objects.py:11-29
 COLORS = {
@@ -73,7 +74,7 @@ class Operand(C.Structure):
 
 class GenOp(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in ("kind", "obj", "count", "x", "y", "w", "h", "max_tries")] + [("reject", C.c_void_p)]
-                + [("a", Operand * 4)])
+                + [("a", Operand * 4), ("cnt", Operand), ("sel_reg", C.c_int32), ("n_sel", C.c_int32), ("sel", C.c_int32 * MAX_SEL)])
 
 
 class Config(C.Structure):
@@ -89,7 +90,7 @@ class Config(C.Structure):
                 ("prestige_beta", C.c_double * MAX_AGENTS), ("prestige_scale", C.c_double * MAX_AGENTS),
                 ("hide_type_mask", C.c_uint32 * MAX_AGENTS),
                 ("spawn_x0", C.c_int32), ("spawn_y0", C.c_int32), ("spawn_x1", C.c_int32), ("spawn_y1", C.c_int32),
-                ("spawn_max_tries", C.c_int32), ("spawn_reject", C.c_void_p)]
+                ("spawn_max_tries", C.c_int32), ("spawn_reject", C.c_void_p), ("param_default", C.c_int32 * MAX_PARAMS)]
 
 
 _lib = None
@@ -133,6 +134,11 @@ def lib():
         L.mgo_get_mt.argtypes = [vp, u32p, i32p]
         L.mgo_get_draws.restype = None
         L.mgo_get_draws.argtypes = [vp, i32p, i32p]
+        L.mgo_get_conds.restype = None
+        L.mgo_get_conds.argtypes = [vp, C.POINTER(C.c_int8)]
+        L.mgo_set_param.restype = None
+        L.mgo_set_param.argtypes = [vp, C.c_int32, C.c_int32]
+        L.mgo_get_param.argtypes = [vp, C.c_int32]
         L.mgo_get_prestige.argtypes = [vp, f64p]
         L.mgo_rich_obs.restype = None
         L.mgo_rich_obs.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), f64p, C.POINTER(C.c_int32)]
@@ -229,19 +235,59 @@ def _sprite(o):
     return []                                           # Floor / Lava / EmptySpace: unrenderable upstream
 
 
-_GEN_KIND = {"wall_rect": 0, "horz_wall": 1, "vert_wall": 2, "put": 3, "place": 4, "draw": 5, "fill": 6, "place_sym": 7}
+_GEN_KIND = {"wall_rect": 0, "horz_wall": 1, "vert_wall": 2, "put": 3, "place": 4, "draw": 5, "fill": 6, "place_sym": 7,
+             "if": 8, "else": 9, "endif": 10, "param": 11}
+
+
+def _operand(o, v):
+    """a value of a gen op that may depend on a `_rand_int` value: an int, or ("d", reg, sign, const) for
+    `const + sign * draw[reg]`"""
+    if isinstance(v, tuple):
+        tag, reg, sign, const = v
+        assert tag == "d" and 0 <= reg < MAX_DRAWS and sign in (1, -1), v
+        o.c, o.reg, o.sign = int(const), int(reg), int(sign)
+    else:
+        o.c, o.reg, o.sign = int(v), -1, 1
 
 
 def _operands(op, vals):
-    """a coordinate of a gen op that may depend on a `_rand_int` value: an int, or ("d", reg, sign, const) for
-    `const + sign * draw[reg]`"""
     for i, v in enumerate(vals):
-        if isinstance(v, tuple):
-            tag, reg, sign, const = v
-            assert tag == "d" and 0 <= reg < MAX_DRAWS and sign in (1, -1), v
-            op.a[i].c, op.a[i].reg, op.a[i].sign = int(const), int(reg), int(sign)
-        else:
-            op.a[i].c, op.a[i].reg, op.a[i].sign = int(v), -1, 1
+        _operand(op.a[i], v)
+
+
+def _object(op, v):
+    """the object of a put / fill / place / place_sym: an id, or ("sel", reg, (id0, id1, ...)) — `lst[draw[reg]]` of a
+    `_rand_elem` over objects"""
+    op.sel_reg = -1
+    if isinstance(v, tuple):
+        tag, reg, ids = v
+        assert tag == "sel" and 0 <= reg < MAX_DRAWS and 0 < len(ids) <= MAX_SEL, v
+        op.sel_reg, op.n_sel = int(reg), len(ids)
+        op.sel[:len(ids)] = [int(i) for i in ids]
+        op.obj = int(ids[0])
+    else:
+        op.obj = int(v)
+
+
+def _count(op, v):
+    op.count = v if isinstance(v, int) else 0
+    _operand(op.cnt, v)
+
+
+def check_blocks(prog):
+    """the ("if", ...) / ("else",) / ("endif",) entries of a program nest properly, at most MAX_DEPTH deep"""
+    open_ = []
+    for g in prog:
+        if g[0] == "if":
+            open_.append(False)
+            assert len(open_) <= MAX_DEPTH, "blocks nested more than %d deep" % MAX_DEPTH
+        elif g[0] == "else":
+            assert open_ and not open_[-1], "else without an if"
+            open_[-1] = True
+        elif g[0] == "endif":
+            assert open_, "endif without an if"
+            open_.pop()
+    assert not open_, "an if without its endif"
 
 
 def reject_mask(cells, W, H):
@@ -334,13 +380,21 @@ def make_config(spec):
         for j, op in enumerate(ops):
             d.fill[j] = op
     cfg.wall_obj = spec["wall_obj"]
+    # per-env parameters of `_gen_grid` (("param", reg, column)): a column is a number or a name of spec["params"], a list
+    # of (name, value every new env holds)
+    cfg._param_names = [p[0] for p in spec.get("params", ())]
+    assert len(cfg._param_names) <= MAX_PARAMS
+    for i, p in enumerate(spec.get("params", ())):
+        cfg.param_default[i] = int(p[1])
     for which, name in enumerate(("gen_ctor", "gen_reset")):
         prog = spec[name]
-        assert len(prog) <= MAX_GEN
+        assert len(prog) <= MAX_GEN, len(prog)
+        check_blocks(prog)
         cfg.n_gen[which] = len(prog)
         for j, g in enumerate(prog):
             op = cfg.gen[which][j]
             op.kind = _GEN_KIND[g[0]]
+            op.sel_reg = -1
             if g[0] == "wall_rect":
                 op.x, op.y, op.w, op.h = g[1:5]
             elif g[0] == "horz_wall":
@@ -348,9 +402,12 @@ def make_config(spec):
             elif g[0] == "vert_wall":
                 op.x, op.y, op.h = g[1:4]
             elif g[0] == "put":
-                op.obj, op.x, op.y = g[1:4]
+                _object(op, g[1])
+                op.x, op.y = g[2:4]
             elif g[0] == "place":
-                op.obj, op.count, op.max_tries = g[1:4]
+                _object(op, g[1])
+                _count(op, g[2])                     # an int, or an operand: that many place_obj calls, below 1 none
+                op.max_tries = g[3]
                 if len(g) >= 8:                      # sampling rectangle [x0,x1) x [y0,y1)
                     op.x, op.y, op.w, op.h = g[4], g[5], g[6] - g[4], g[7] - g[5]
                 if len(g) == 9 and g[8]:             # reject_fn, tabulated: the rejected cells ((x, y), ...)
@@ -362,11 +419,21 @@ def make_config(spec):
                 assert 0 <= g[1] < MAX_DRAWS
                 _operands(op, g[2:4])
             elif g[0] == "fill":                     # ("fill", obj, x0, y0, x1, y1): grid.set over [x0, x1) x [y0, y1)
-                op.obj = g[1]
+                _object(op, g[1])
                 _operands(op, g[2:6])
             elif g[0] == "place_sym":                # ("place_sym", obj, count, max_tries, x0, y0, x1, y1): top, top + size
-                op.obj, op.count, op.max_tries = g[1:4]
+                _object(op, g[1])
+                _count(op, g[2])
+                op.max_tries = g[3]
                 _operands(op, g[4:8])
+            elif g[0] == "if":                       # ("if", value, lo, hi): `if lo <= value <= hi:` ... ("else",) ... ("endif",)
+                _operands(op, g[1:4])
+            elif g[0] == "param":                    # ("param", r, column): draw[r] = the env's parameter, no RNG word
+                op.obj = g[1]
+                assert 0 <= g[1] < MAX_DRAWS
+                col = cfg._param_names.index(g[2]) if isinstance(g[2], str) else int(g[2])
+                assert 0 <= col < MAX_PARAMS
+                _operands(op, (col,))
     return cfg
 
 
@@ -475,6 +542,25 @@ class OracleEnv(object):
         d, w = np.zeros(MAX_DRAWS, np.int32), np.zeros(MAX_DRAWS, np.int32)
         self.L.mgo_get_draws(self.h, _p(d, C.c_int32), _p(w, C.c_int32))
         return d, w
+
+    def conds(self):
+        """the `if` entries of the program the last `_gen_grid` ran, by their index in it: 1 the condition held, 0 it did not,
+        -1 not evaluated (no `if`, or inside a block that was not taken)"""
+        c = np.zeros(MAX_GEN, np.int8)
+        self.L.mgo_get_conds(self.h, _p(c, C.c_int8))
+        return c
+
+    def _param_index(self, column):
+        return self.cfg._param_names.index(column) if isinstance(column, str) else int(column)
+
+    def set_params(self, _columns=None, **values):
+        """set_params(n=3), or set_params({0: 3}) by column number: per-env parameters of `_gen_grid`, taken as given; the
+        env's next reset reads them (a running episode is untouched)"""
+        for column, v in dict(_columns or {}, **values).items():
+            self.L.mgo_set_param(self.h, self._param_index(column), int(v))
+
+    def param(self, column):
+        return int(self.L.mgo_get_param(self.h, self._param_index(column)))
 
     def set_dir(self, k, d):
         self.L.mgo_set_agent_dir(self.h, k, d)

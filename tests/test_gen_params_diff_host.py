@@ -1,6 +1,6 @@
 """CPU: `reset_env` with PARAM ops and symbolic counts (marlgrid_amd/csrc/mg_core.h, built for the host) — a batch whose envs
 hold different parameter values against the constant TWINS of tests/param_envs.py, env by env, and the twins against the CPU
-oracle, so that `parameter env == twin == oracle == reference` closes.  The parameter table lies behind the template as on
+oracle (all four kinds: it reads their forks as `if` blocks), so that `parameter env == twin == oracle == reference` closes.  The parameter table lies behind the template as on
 the device (tests/native/hostemu_params.py).
 
 The constructor's reset of a parameter env runs with the defaults and draws other RNG words than a twin's: both sides are
@@ -68,23 +68,20 @@ def test_mixed_batch_equals_the_twins_env_by_env(kind):
     assert (emu._last_prog._keep[-64:] == 0xA5).all()
 
 
-# the twins whose programs the oracle reads: no guard in them (oracle/oracle.py replays draws, fills and placements, not the
-# branches of a fork — `kind` and `long` fork on a `_rand_bool` in the twin as well)
-ORACLE_TWINS = [(kind, v) for kind in ("clutter", "split") for v in range(*PE.interval(kind))]
+# the twins against the oracle, every value of every kind: the oracle runs the hand-written twin spec (tests/param_envs.py:spec
+# — an `if` block where `kind` and `long` fork on a `_rand_bool`), not what the product's recorder made of the twin
+ORACLE_TWINS = [(kind, v) for kind in sorted(PE.KINDS) for v in range(*PE.interval(kind))]
 
 
 @pytest.mark.parametrize("kind,v", ORACLE_TWINS, ids=["%s-%d" % c for c in ORACLE_TWINS])
 def test_twins_against_the_oracle(kind, v):
-    import draw_envs as D
     import hostemu
     import wide_diff
     PE.register()
     Bn = 64
     seeds = SEED0 + np.arange(Bn)
     sub = wide_diff.HostEmuSubject(hostemu.HostEmu(PE.name_of(kind, v), Bn, seeds, auto_reset=True, par=True, max_steps=MAX_STEPS))
-    spec = D.decode_spec(sub.spec)
-    assert not any(e[0] in ("guard", "param") for e in spec["gen_reset"])
-    out = wide_diff.run(sub, PE.name_of(kind, v), seeds, T, deep_every=20, spec=spec)
+    out = wide_diff.run(sub, PE.name_of(kind, v), seeds, T, deep_every=20, spec=PE.spec(kind, v, max_steps=MAX_STEPS))
     assert out["episodes"].min() >= T // MAX_STEPS - 1
 
 

@@ -1,7 +1,8 @@
 """Every `_gen_grid` recording the project knows, pinned: the template bytes, the recorded ops (reject tables by CRC), the op
 count and `scenario_spec()`'s gen_ctor / gen_reset / objects of each scenario equal tests/golden/gen_recordings.json — the
 recorder's own output, written by `python tests/test_gen_recording_pinned.py --write` on the commit BEFORE the recorder moved
-out of MultiGridEnv into marlgrid_amd/gen_recorder.py.  Regenerate the table only with a change that means to alter a
+out of MultiGridEnv into marlgrid_amd/gen_recorder.py (since then, by changes of the scenarios themselves: the entry of
+`Branch-2AgentDeep12x10` added; the Box of `Param-kind` and its twins made a Key — their `objects` alone).  Regenerate the table only with a change that means to alter a
 recorded program, and review its diff.  Host only: every env is built `_dry`."""
 import json
 import os
@@ -12,7 +13,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 TABLE = os.path.join(HERE, "golden", "gen_recordings.json")
-MIN_NAMES = 116     # 65 ids in the registry (the package's and the test modules') + 32 test scenarios + 9 draw + 6 branch + 4 parameter
+MIN_NAMES = 117     # 66 ids in the registry (the package's and the test modules') + 32 test scenarios + 9 draw + 6 branch + 4 parameter
 
 
 def _plain(v):

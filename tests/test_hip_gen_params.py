@@ -47,7 +47,7 @@ def test_mixed_batch_equals_the_twins(kind, path, mode):
     lo, hi = PE.interval(kind)
     vals = PE.values(kind, B)
     seeds = 7100 + np.arange(B)
-    # (strict=False: `kind` places a Box, and toggling one is the reference's TypeError — recorded per env, compared like the rest)
+    # (strict=False: an error of the reference's would be recorded per env and compared like the rest)
     kw = dict(batch_size=B, seeds=seeds, place_obs=False, auto_reset=MODES[mode], max_steps=10, strict=False, **PATHS[path])
     env = PE.build(kind, **kw)
     rows = {v: torch.from_numpy(np.nonzero(vals == v)[0]).to(env.device) for v in range(lo, hi)}

@@ -297,12 +297,14 @@ class _EpisodeRef(object):
 
 # ---- the driver ---------------------------------------------------------------------------------------------------------
 def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mode="same_step", episode_info=False,
-        obs_format="image", stagger=False, after_step=None, spec=None, watch=None):
+        obs_format="image", stagger=False, after_step=None, spec=None, watch=None, between=None):
     """Step `subject` and the oracle of `spec` (default: scenarios.registered(name)) for T steps (actions
     RandomState(action_seed).randint(0, 7)).
     watch(t, envs, mask): called with the ORACLE's envs after every reset on its side — t = 0: reset() (mask: everyone);
     after step t: the envs whose reset ran in that call (same-step mode: those that ended in it; next-step mode: those that had
     ended in the call before); after a staggered reset by hand.  What a test requires of its own coverage it reads there.
+    between(t, subject, envs): called with the subject and the ORACLE's envs before the first reset (t = 0) and after step t and
+    all of its checks — where a run calls `set_params` on both sides: a value takes effect at an env's next reset on either.
     mode: the subject's auto-reset mode; stagger: during the first 100 steps env b is reset by hand after step b % 100 (0-based),
     subject and oracle; after_step(t, subject): called between two steps (fault injection in the driver's own tests).
     -> dict(episodes (B,), draws (B,) RNG words drawn per env, blocks = draws / 624, partial_done_steps: steps on which some
@@ -402,6 +404,8 @@ def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mo
         lap("deep")
 
     # -- the constructor's reset has run on both sides; one reset() more, as every caller of the env does
+    if between is not None:
+        between(0, subject, envs)
     obs = subject.reset()
     ref.reset()
     last_pos = subject.mt_pos().astype(np.int64)
@@ -476,6 +480,9 @@ def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mo
                 check_obs(t, obs, None, ids=np.nonzero(mask)[0], what="observations of reset(env_mask)")
         if after_step is not None:
             after_step(t, subject)
+            clock[0] = time.time()
+        if between is not None:
+            between(t, subject, envs)
             clock[0] = time.time()
     subject.check_errors()
     return dict(episodes=episodes, draws=draws, blocks=draws / float(MT_N), partial_done_steps=partial,

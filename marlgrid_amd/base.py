@@ -22,7 +22,7 @@ Differences from the reference that the batch forces (documented in DESIGN.md):
     own RNG, so scenario subclasses written against the reference API keep working; layout logic
     that branches on a random draw in Python says so with `self._fork(draw)` (or draws through
     `_rand_elem` / `_rand_bool`) and is recorded once per value — the recorder, its op type and the
-    packing of a program are marlgrid_amd/gen_recorder.py;
+    packing of a program are marlgrid_amd/gen_recorder.py (the parameter table: gen_params.py; replayable levels: levels.py);
   * per-env runtime errors (the reference's exceptions) are collected in `error` and raised as the
     matching Python exception after the step (strict=True) or on `check_errors()`.
 """
@@ -33,15 +33,16 @@ import os
 import numpy as np
 
 from . import _native as N
-from . import rendering, seeding, spaces
+from . import per_env, rendering, seeding, spaces
 from .agents import GridAgentInterface
+from .gen_params import ParamTable
 from .gen_recorder import GenDraw, GenRecorder, _NO_BRANCH, _any_draw, _gen_add, _trace, decode_program, pack_program
+from .levels import EnvLevels, LevelBank
 from .objects import COLOR_TO_IDX, OBJECT_TYPES, BonusTile, Box, Door, Goal, Key, Wall, WorldObj
 
 TILE_PIXELS = 32
 DEFAULT_PLACE_OBS = "search"
 STATE_DICT_VERSION = 3              # the C ABI version that last changed the MgState layout / RNG form the tensors follow
-
 
 
 def _on_device(fn):
@@ -428,144 +429,6 @@ class _ViewGroup(object):
         self.spec_info = {}                              # ... and what the library said about it (MgSpecInfo as a dict)
 
 
-class LevelBank(object):
-    """Replayable levels: L freshly seeded generators on one device.  A level is a seed; playing it is the reference's
-    `env.seed(s); env.reset()` (base.py:371-374, 402-416) — layout, agent placement and every later draw of the episode come
-    from a generator seeded with s.  `mt` (L, 624), `pos` (L,), `head` (L, 16): what mg_mt_seed leaves per env; `seeds` (L,)
-    int64, -1 = empty slot.  `seeds_or_capacity`: an int — that many empty slots — or the slots' seeds (-1: empty).
-    An env is pointed at slots with `env.set_levels(bank, ids)` and takes a copy of its slot's generator at its next reset;
-    `assign` replaces levels.  Seeds are hashed and the generators seeded on the device (mg_level_seed)."""
-
-    def __init__(self, seeds_or_capacity, device=None, _dry=False):
-        self._dry = bool(_dry)
-        self._replicas = {}         # device -> the copy of this bank a shard on that device reads (sharding._Shards.set_levels)
-        self._readers = {}          # streams that read this bank's rows (an env's mg_level_apply): what `assign` orders itself with
-        self.launches = 0
-        first = None
-        if isinstance(seeds_or_capacity, (int, np.integer)) and not isinstance(seeds_or_capacity, bool):
-            L = int(seeds_or_capacity)
-        else:
-            first = seeds_or_capacity
-            L = int(first.shape[0]) if hasattr(first, "shape") and len(first.shape) == 1 else len(first)
-        if L < 1:
-            raise ValueError("LevelBank: at least one slot")
-        self.capacity = L
-        if self._dry:
-            self.device = None
-            self.seeds = np.full(L, -1, np.int64)
-        else:
-            import torch
-            self.device = torch.device(device if device is not None else "cuda")
-            if self.device.type != "cuda":
-                raise RuntimeError("marlgrid_amd runs on HIP devices only (got %r)" % (device,))
-            if self.device.index is None:
-                self.device = torch.device("cuda", torch.cuda.current_device())
-            self._lib = N.lib()
-            with torch.cuda.device(self.device):
-                self.mt = torch.zeros((L, N.MT_N), dtype=torch.int32, device=self.device)
-                self.pos = torch.zeros((L,), dtype=torch.int32, device=self.device)
-                self.head = torch.zeros((L, N.MT_HEAD), dtype=torch.int32, device=self.device)
-                self.seeds = torch.full((L,), -1, dtype=torch.int64, device=self.device)
-        if first is not None:
-            self.assign(None, first)
-
-    def __len__(self):
-        return self.capacity
-
-    @staticmethod
-    def _host_ints(v, what):
-        """host values -> int64 ndarray (python ints up to 2**63 - 1 included); ValueError for anything that is no integer"""
-        a = np.asarray(v.cpu() if hasattr(v, "cpu") else v)
-        if a.dtype == object:
-            try:
-                a = a.astype(np.int64)
-            except (OverflowError, TypeError, ValueError):
-                raise ValueError("%s: integers in [-1, 2**63 - 1]" % what)
-        if a.dtype.kind not in "iu" or a.dtype == bool:
-            raise ValueError("%s: integer values, not %s" % (what, a.dtype))
-        if a.dtype == np.uint64 and a.size and a.max() > np.uint64(2 ** 63 - 1):
-            raise ValueError("%s: integers in [-1, 2**63 - 1]" % what)
-        return a.astype(np.int64)
-
-    @classmethod
-    def _check_seeds(cls, seeds, what):
-        a = cls._host_ints(seeds, what)
-        if a.size and a.min() < -1:
-            raise ValueError("%s: a seed is >= 0, or -1 for none (got %d)" % (what, a.min()))
-        return a
-
-    def _is_dev(self, v):
-        return not self._dry and hasattr(v, "is_cuda") and v.is_cuda
-
-    def assign(self, slots, seeds):
-        """Put `seeds` (k,) into `slots` (k,) — None: slots 0 .. k-1 —, in stream order: the envs pointed at a slot play its new
-        level from their next reset on.  -1 empties a slot (its envs run free).  Device int64 tensors: one launch, nothing is
-        read back, and two entries naming one slot are the caller's error; host values are checked (ValueError for a slot
-        outside the bank, a seed < -1, a slot named twice)."""
-        L = self.capacity
-        if self._is_dev(seeds) and (slots is None or self._is_dev(slots)):
-            if seeds.dim() != 1 or (slots is not None and tuple(slots.shape) != tuple(seeds.shape)):
-                raise ValueError("LevelBank.assign: slots and seeds of one shape (k,)")
-        else:
-            seeds = self._check_seeds(seeds, "LevelBank.assign(seeds=)").reshape(-1)
-            if slots is not None:
-                slots = self._host_ints(slots, "LevelBank.assign(slots=)").reshape(-1)
-                if slots.shape != seeds.shape:
-                    raise ValueError("LevelBank.assign: slots and seeds of one shape (k,)")
-                if slots.size and (slots.min() < 0 or slots.max() >= L):
-                    raise ValueError("LevelBank.assign: slots outside 0..%d" % (L - 1))
-                if len(np.unique(slots)) != slots.size:
-                    raise ValueError("LevelBank.assign: a slot is named twice")
-            elif seeds.size > L:
-                raise ValueError("LevelBank.assign: %d seeds for %d slots" % (seeds.size, L))
-            if self._dry:
-                self.seeds[np.arange(seeds.size) if slots is None else slots] = seeds
-                return
-        self._seed_rows(seeds, slots, None)
-        for rep in self._replicas.values():
-            rep.assign(slots, seeds)
-
-    def _seed_rows(self, seeds, slots, mask):
-        """mg_level_seed on torch's current stream of the bank's device, ordered against the streams that read the bank"""
-        import torch
-        with torch.cuda.device(self.device):
-            def dev(v):
-                if v is None:
-                    return None
-                v = v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))
-                return v.to(device=self.device, dtype=torch.int64).contiguous()
-            seeds, slots = dev(seeds), dev(slots)
-            cur = torch.cuda.current_stream(self.device)
-            others = [r for r in self._readers.values() if r != cur]
-            for r in others:                        # rows an earlier step's launch still reads are not overwritten under it
-                cur.wait_event(r.record_event())
-            N.check(self._lib.mg_level_seed(int(seeds.shape[0]), seeds.data_ptr(), None if slots is None else slots.data_ptr(),
-                                            None if mask is None else mask.data_ptr(), self.capacity, self.mt.data_ptr(),
-                                            self.pos.data_ptr(), self.head.data_ptr(), self.seeds.data_ptr(), C.c_void_p(cur.cuda_stream)))
-            self.launches += 1
-            if others:
-                ev = cur.record_event()
-                for r in others:
-                    r.wait_event(ev)
-
-    def replica(self, device, streams=()):
-        """this bank's levels on `device`, for shards that live there and step on `streams`: seeded there from `seeds` (one
-        launch, no generator crosses devices) and kept up to date by `assign`"""
-        import torch
-        device = torch.device(device)
-        rep = self._replicas.get(device)
-        if rep is None:
-            rep = LevelBank(self.capacity, device)
-            for s in streams:
-                rep._readers[s.cuda_stream] = s
-            with torch.cuda.device(device):
-                rep._seed_rows(self.seeds.to(device), None, None)
-            self._replicas[device] = rep
-        for s in streams:
-            rep._readers[s.cuda_stream] = s
-        return rep
-
-
 class MultiGridEnv(object):
     """See module docstring.  Constructor keeps the reference's kwargs (base.py:335-347) and adds
     `batch_size`, `device`, `seeds`, `auto_reset`, `strict`."""
@@ -700,19 +563,12 @@ class MultiGridEnv(object):
         self._settings_seen = None
         self._gen = GenRecorder(self)       # all `_gen_grid` recording state and logic (gen_recorder.py)
         self._prog_cache = {}
-        self._param_decl = {}       # `_param` names of this env's `_gen_grid`: name -> dict(col, lo, hi, default); columns stay
-        self._param_buf = None      # the template of a program with a PARAM op and, behind it, the table (marlgrid_hip.h)
-        self._param_tpl = None      # ... the template bytes the buffer holds now
-        self.params_t = None        # the table: (B, MG_GEN_DRAWS) uint8 — a view of the buffer's tail (a numpy array when _dry)
+        self._params = ParamTable(self)     # the per-env parameters of `_gen_grid` (gen_params.py)
+        self._levels = EnvLevels(self)      # replayable levels (levels.py): nothing is allocated or launched until set_levels
         self._spec_ctor = None
         self._spec_last = None
         self._probe = None
         self.grid = None
-        # replayable levels (set_levels): nothing is allocated or launched until it is first called
-        self._levels_on = False
-        self._level_launches = 0
-        self._level_bank = self._own_bank = None
-        self._level_of_env = None
 
         if not self._dry:
             import torch
@@ -1130,36 +986,16 @@ class MultiGridEnv(object):
         return self._gen.param(name, low, high, default)
 
     def _param_column(self, name, low, high, default):
-        """the table column of parameter `name`: its own from the first time `_gen_grid` names it on, filled with `default`
-        then; the values set since survive every later recording"""
-        d = self._param_decl.get(name)
-        if d is None:
-            if len(self._param_decl) >= N.GEN_DRAWS:
-                raise NotImplementedError("_gen_grid has named more than %d parameters: the table has %d columns (MG_GEN_DRAWS)"
-                                          % (N.GEN_DRAWS, N.GEN_DRAWS))
-            if self.params_t is None:
-                if self._dry:
-                    self.params_t = np.zeros((self.batch_size, N.GEN_DRAWS), np.uint8)
-                else:
-                    import torch
-                    self._param_buf = torch.zeros(self.cells_stride + self.batch_size * N.GEN_DRAWS, dtype=torch.uint8,
-                                                  device=self.device)
-                    self.params_t = self._param_buf[self.cells_stride:].view(self.batch_size, N.GEN_DRAWS)
-            d = self._param_decl[name] = dict(col=len(self._param_decl), lo=low, hi=high, default=default)
-            if self._dry:
-                self.params_t[:, d["col"]] = default
-            else:
-                self.params_t[:, d["col"]].fill_(default)
-        else:
-            d.update(lo=low, hi=high, default=default)      # (what the table holds is clamped to the interval where it is loaded)
-        return d["col"]
+        return self._params.column(name, low, high, default)
+
+    params_t = property(lambda self: self._params.table)    # (B, MG_GEN_DRAWS) uint8; None until `_gen_grid` names a parameter
 
     @property
     def params(self):
         """name -> (B,) uint8: the column of the parameter table that `_gen_grid`'s `self._param(name, ...)` reads (a view:
         `set_params` validates what it writes, a direct write is clamped on the device when it is loaded)"""
         self._ensure_recorded()
-        return {name: self.params_t[:, d["col"]] for name, d in self._param_decl.items()}
+        return {name: self.params_t[:, d["col"]] for name, d in self._params.decl.items()}
 
     @_on_device
     def _ensure_recorded(self):
@@ -1180,124 +1016,12 @@ class MultiGridEnv(object):
         Host values are checked against the parameter's interval (ValueError); a device tensor is clamped to it in stream
         order, without a host synchronisation.  A value takes effect when its env next resets — reset(), the reset inside a
         step launch, a next-step reset —: the running episode is untouched."""
-        if env_mask is not None and env_ids is not None:
-            raise ValueError("set_params: env_mask or env_ids, not both")
-        self._ensure_recorded()
-        B = self.batch_size
-        for name in values:
-            if name not in self._param_decl:
-                raise KeyError("set_params: %r is no parameter of this env's _gen_grid (declared: %s)"
-                               % (name, ", ".join(sorted(self._param_decl)) or "none"))
-        torch = None
-        if not self._dry:
-            import torch
-        if env_mask is not None:
-            if torch is not None and torch.is_tensor(env_mask):
-                mask = env_mask.to(self.device).bool()
-            else:
-                mask = np.asarray(env_mask).astype(bool)
-            if tuple(mask.shape) != (B,):
-                raise ValueError("env_mask must have shape (batch_size,)")
-            if torch is not None and not torch.is_tensor(mask):
-                mask = torch.from_numpy(mask).to(self.device)
-        if env_ids is not None:
-            if torch is not None and torch.is_tensor(env_ids):
-                ids = env_ids.to(self.device).long()
-            else:
-                ids = np.asarray(env_ids).astype(np.int64).reshape(-1)
-                if ids.size and (ids.min() < 0 or ids.max() >= B):
-                    raise ValueError("set_params: env_ids outside 0..%d" % (B - 1))
-                if torch is not None:
-                    ids = torch.from_numpy(ids).to(self.device)
-            k = int(ids.shape[0])
-        for name, v in values.items():
-            d = self._param_decl[name]
-            col = self.params_t[:, d["col"]]
-            if torch is not None and torch.is_tensor(v) and v.is_cuda:
-                v = v.to(self.device).clamp(d["lo"], d["hi"] - 1).to(torch.uint8)
-            else:
-                v = np.asarray(v.cpu() if torch is not None and torch.is_tensor(v) else v)
-                if v.dtype.kind not in "iu" or v.dtype == bool:
-                    raise ValueError("set_params(%s=): integer values, not %s" % (name, v.dtype))
-                if v.size and (v.min() < d["lo"] or v.max() >= d["hi"]):
-                    raise ValueError("set_params(%s=): values %d..%d outside the parameter's interval [%d, %d)"
-                                     % (name, v.min(), v.max(), d["lo"], d["hi"]))
-                v = v.astype(np.uint8)
-                if torch is not None:
-                    v = torch.from_numpy(v if v.ndim == 0 else np.ascontiguousarray(v)).to(self.device)     # (ascontiguousarray: ndim >= 1)
-            want = (B,) if env_ids is None else (k,)
-            if v.ndim == 1 and env_ids is not None and tuple(v.shape) == (B,) != want:
-                v = v[ids]
-            if v.ndim != 0 and tuple(v.shape) != want:
-                raise ValueError("set_params(%s=): an int or one value per env, shape %s; got %s" % (name, want, tuple(v.shape)))
-            if env_ids is not None:
-                col[ids] = v
-            elif env_mask is not None:
-                if torch is not None:
-                    col.copy_(torch.where(mask, v, col))
-                else:
-                    col[...] = np.where(mask, v, col)
-            elif torch is not None:
-                col.copy_(v.expand(B) if v.ndim == 0 else v)
-            else:
-                col[...] = v
+        self._params.set(env_mask, env_ids, **values)
 
     # ---- replayable levels ----------------------------------------------------------------------------------------------
     def level_bank(self, seeds_or_capacity):
         """a LevelBank on this env's device"""
         return LevelBank(seeds_or_capacity, None if self._dry else self.device, _dry=self._dry)
-
-    def _enable_levels(self):
-        """the tensors of set_levels, made at its first call: an env that never calls it allocates and launches nothing"""
-        if self._levels_on:
-            return
-        if self.auto_reset_mode == "same_step":
-            raise ValueError("set_levels: with auto_reset=True a same-step reset happens inside the launch that ends the episode, "
-                             "where no level can be handed over; construct the env with auto_reset='next_step' (or False)")
-        self._levels_on = True
-        if self._dry:
-            self._level_of_env = np.full(self.batch_size, -1, np.int64)
-            return
-        import torch
-        B, dev = self.batch_size, self.device
-        self._level_of_env = torch.full((B,), -1, dtype=torch.int64, device=dev)
-        for r in self._ring:
-            r["level"] = torch.full((B,), -1, dtype=torch.int64, device=dev)
-            if "info" in r:
-                r["info"]["level"] = r["level"]
-
-    def _select_envs(self, env_mask, env_ids, who):
-        """(mask, ids) of a per-env setter, checked: at most one of them; device tensors where the env has a device"""
-        if env_mask is not None and env_ids is not None:
-            raise ValueError("%s: env_mask or env_ids, not both" % who)
-        B = self.batch_size
-        torch = None
-        if not self._dry:
-            import torch
-        mask = ids = None
-        if env_mask is not None:
-            if torch is not None and torch.is_tensor(env_mask):
-                mask = env_mask.to(self.device)
-            else:
-                mask = np.asarray(env_mask)
-            if tuple(mask.shape) != (B,):
-                raise ValueError("env_mask must have shape (batch_size,)")
-            if torch is not None:
-                mask = (mask if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(mask)).to(self.device))
-                # (bytes 0 / 1: a bool tensor — step()'s `done` — is taken as it is, no launch)
-                mask = (mask if mask.dtype == torch.bool else mask != 0).contiguous().view(torch.uint8)
-            else:
-                mask = mask.astype(bool)
-        if env_ids is not None:
-            if torch is not None and torch.is_tensor(env_ids) and env_ids.is_cuda:
-                ids = env_ids.to(self.device).long().reshape(-1)
-            else:
-                ids = LevelBank._host_ints(env_ids, "%s(env_ids=)" % who).reshape(-1)
-                if ids.size and (ids.min() < 0 or ids.max() >= B):
-                    raise ValueError("%s: env_ids outside 0..%d" % (who, B - 1))
-                if torch is not None:
-                    ids = torch.from_numpy(ids).to(self.device)
-        return mask, ids
 
     @_on_device
     def set_levels(self, bank=None, ids=None, seeds=None, env_mask=None, env_ids=None):
@@ -1313,99 +1037,17 @@ class MultiGridEnv(object):
         Host values are checked (ValueError); device tensors are only range-guarded on the device, and with them the call reads
         nothing back.  Needs auto_reset=False or "next_step".  `env.episode_level` (B,) int64 is the seed of the level each
         env's running episode was started from (-1: free-running); with episode_info, info["level"] is the step's copy."""
-        who = "set_levels"
-        if (bank is None) == (seeds is None) or (bank is not None and ids is None) or (seeds is not None and ids is not None):
-            raise ValueError("set_levels: either (bank, ids) or seeds=")
-        mask, eids = self._select_envs(env_mask, env_ids, who)
-        self._enable_levels()
-        B = self.batch_size
-        torch = None
-        if not self._dry:
-            import torch
-        if bank is not None:
-            if not isinstance(bank, LevelBank):
-                raise ValueError("set_levels: bank must be a LevelBank")
-            if not self._dry and bank.device != self.device:
-                raise ValueError("set_levels: the bank lives on %s, the env on %s (env.level_bank(...) makes one here)" % (bank.device, self.device))
-            v, lo, hi, what = ids, -1, bank.capacity, "ids"
-        else:
-            v, lo, hi, what = seeds, -1, None, "seeds"
-        if torch is not None and torch.is_tensor(v) and v.is_cuda:
-            v = v.to(self.device).long()
-        else:
-            v = LevelBank._host_ints(v, "set_levels(%s=)" % what)
-            if v.size and (v.min() < lo or (hi is not None and v.max() >= hi)):
-                raise ValueError("set_levels(%s=): values %d..%d outside [%d, %s)" % (what, v.min(), v.max(), lo, hi if hi is not None else "2**63"))
-            if torch is not None:
-                v = torch.from_numpy(v if v.ndim == 0 else np.ascontiguousarray(v)).to(self.device)     # (ascontiguousarray: ndim >= 1)
-        k = None if eids is None else int(eids.shape[0])
-        want = (B,) if k is None else (k,)
-        if v.ndim == 1 and k is not None and tuple(v.shape) == (B,) != want:
-            v = v[eids]
-        if v.ndim != 0 and tuple(v.shape) != want:
-            raise ValueError("set_levels(%s=): an int or one value per env, shape %s; got %s" % (what, want, tuple(v.shape)))
-        partial = mask is not None or eids is not None
-        if bank is None:
-            if self._own_bank is None:
-                self._own_bank = self.level_bank(B)
-            bank = self._own_bank
-        if bank is not self._level_bank:
-            if partial and self._level_bank is not None:
-                raise ValueError("set_levels: the envs of one batch read one bank at a time; change to another bank (or between a "
-                                 "bank and seeds=) with a call for every env")
-            self._level_bank = bank
-            if bank is self._own_bank:      # row b is env b's: whether it plays a level is whether its row is filled
-                if self._dry:
-                    self._level_of_env[:] = np.arange(B)
-                    bank.seeds[:] = -1
-                else:
-                    torch.arange(B, out=self._level_of_env)
-                    bank.seeds.fill_(-1)
-        if self._dry:
-            dst = bank.seeds if bank is self._own_bank else self._level_of_env
-            if eids is not None:
-                dst[eids] = v
-            elif mask is not None:
-                dst[...] = np.where(mask, v, dst)
-            else:
-                dst[...] = v
-            return
-        if bank is self._own_bank:
-            if v.ndim == 0:
-                v = v.expand(want).contiguous()
-            bank._readers.update(self._launch_streams)
-            bank._seed_rows(v, eids, mask)
-        elif eids is not None:
-            self._level_of_env[eids] = v
-        elif mask is not None:
-            torch.where(mask.view(torch.bool), v, self._level_of_env, out=self._level_of_env)
-        else:
-            self._level_of_env.copy_(v.expand(B) if v.ndim == 0 else v)
-
-    def _apply_levels(self, rule, mask_ptr, stream):
-        """mg_level_apply in front of a reset or a step: the envs the rule selects take their level's generator; every env's
-        running level goes to the current buffer set.  Nothing unless set_levels was ever called."""
-        bank = self._level_bank
-        if not self._levels_on or self._dry or bank is None:
-            return
-        bank._readers.update(self._launch_streams)
-        N.check(self._lib.mg_level_apply(C.byref(self._cfg), C.byref(self._state), rule, mask_ptr, self._level_of_env.data_ptr(),
-                                         bank.capacity, bank.mt.data_ptr(), bank.pos.data_ptr(), bank.head.data_ptr(), bank.seeds.data_ptr(),
-                                         self.episode_level.data_ptr(), self._ring[self._ring_i]["level"].data_ptr(), stream))
-        self._level_launches += 1
+        self._levels.set(bank, ids, seeds, env_mask, env_ids)
 
     @property
     def episode_level_t(self):      # (the name state_dict() saves it under)
         return self.episode_level
 
-    def _level_next(self):
-        """(B,) int64: the seed each env's next reset will use, resolved through the bank (-1: free-running)"""
-        import torch
-        bank, lv = self._level_bank, self._level_of_env
-        if bank is None:
-            return torch.full_like(lv, -1)
-        ok = (lv >= 0) & (lv < bank.capacity)
-        return torch.where(ok, bank.seeds[lv.clamp(0, bank.capacity - 1)], torch.full_like(lv, -1))
+    _levels_on = property(lambda self: self._levels.on)                 # the names tests and tools read `env._levels` by
+    _level_launches = property(lambda self: self._levels.launches)
+    _level_bank = property(lambda self: self._levels.bank)
+    _own_bank = property(lambda self: self._levels.own_bank)
+    _level_of_env = property(lambda self: self._levels.level_of_env)
 
     # ---- branching on a draw: one recorded run of `_gen_grid` per path, merged into one guarded program --------------
     def _fork(self, d):
@@ -1759,11 +1401,11 @@ class MultiGridEnv(object):
         # a program with a PARAM op reads the env's parameter table right behind its template: all such programs of this env
         # share ONE buffer — template, then table —, whose head is rewritten (in stream order) when the template changes
         has_param = any(op.is_param for op in ops)
-        if has_param and self._param_tpl != key[0]:
+        if has_param and self._params.tpl != key[0]:
             t = np.zeros(self.cells_stride, np.uint8)
             t[:self.width * self.height] = template.reshape(-1)
-            self._param_buf[:self.cells_stride].copy_(torch.from_numpy(t).to(self.device))
-            self._param_tpl = key[0]
+            self._params.buf[:self.cells_stride].copy_(torch.from_numpy(t).to(self.device))
+            self._params.tpl = key[0]
         prog = self._prog_cache.get(key)
         if prog is not None:
             return prog
@@ -1771,7 +1413,7 @@ class MultiGridEnv(object):
         # the struct carries a raw device pointer: the tensor it points at is kept on the struct
         # itself, so it lives exactly as long as any holder of the program (cache, `_reset_prog`)
         if has_param:
-            prog._template_dev = self._param_buf
+            prog._template_dev = self._params.buf
         else:
             t = np.zeros(self.cells_stride, np.uint8)
             t[:self.width * self.height] = template.reshape(-1)
@@ -1793,10 +1435,14 @@ class MultiGridEnv(object):
         if env_mask is None:
             return None
         import torch
-        m = torch.as_tensor(env_mask, device=self.device)
-        if m.shape != (self.batch_size,):
-            raise ValueError("env_mask must have shape (batch_size,)")
-        self._mask_keep = m.to(torch.uint8).contiguous()
+        if per_env.on_device(env_mask, self.device) and env_mask.dtype == torch.uint8:
+            # bytes as they are (the kernels test nonzero): handed `done_t` itself, mg_reset keeps the done flags readable
+            per_env.check_selectors(self.batch_size, env_mask, None, "env_mask")
+            self._mask_keep = env_mask.to(self.device).contiguous()
+        else:
+            self._mask_keep = per_env.select(self.batch_size, self.device, env_mask, None, "env_mask")[0]
+            if self._mask_keep.data_ptr() == self.done_t.data_ptr():       # step()'s bool `done`: a copy, so that mg_reset
+                self._mask_keep = self._mask_keep.clone()                   # clears the flags of the envs it resets
         return C.c_void_p(self._mask_keep.data_ptr())
 
     # ---- the gym surface -----------------------------------------------------------------------------
@@ -1813,7 +1459,7 @@ class MultiGridEnv(object):
         prog = self._program(template, ops)
         self._reset_prog, self._retrace = prog, False
         mask_ptr, stream = self._mask_ptr(env_mask), self._stream()
-        self._apply_levels(N.LEVEL_MASK, mask_ptr, stream)       # (set_levels: the envs that reset take their level's generator first)
+        self._levels.apply(N.LEVEL_MASK, mask_ptr, stream)       # (set_levels: the envs that reset take their level's generator first)
         N.check(self._lib.mg_reset(C.byref(self._cfg), C.byref(self._state), C.byref(prog), mask_ptr, stream))
         if self.ep_return_t is not None:       # (mg_reset knows nothing of the episode accumulators)
             if env_mask is None:
@@ -1869,8 +1515,8 @@ class MultiGridEnv(object):
             probe(0)
         # obs / rewards / done are views of the current buffer set (see `obs_buffers`)
         done = self.done_b
-        if self._levels_on:     # the same call every step: which envs are about to reset is decided on the device
-            self._apply_levels(N.LEVEL_PENDING if self.auto_reset_mode == "next_step" else N.LEVEL_PUBLISH, None, stream)
+        if self._levels.on:     # the same call every step: which envs are about to reset is decided on the device
+            self._levels.apply(N.LEVEL_PENDING if self.auto_reset_mode == "next_step" else N.LEVEL_PUBLISH, None, stream)
         r = self._ring[self._ring_i] if self._use_ep else None
         self._launch_step(actions, prog, stream, probe, None if r is None else C.byref(r["ep"]))
         info = {}
@@ -2215,7 +1861,7 @@ class MultiGridEnv(object):
         Moving an agent this way gives it the highest arrival rank (as a fresh placement would)."""
         import torch
         m = torch.ones(self.batch_size, dtype=torch.bool, device=self.device) if env_mask is None else \
-            torch.as_tensor(env_mask, device=self.device).bool()
+            per_env.select(self.batch_size, self.device, env_mask, None, "set_agent")[0].view(torch.bool)
         rec = self.agent_state
 
         def setb(col, i, v):
@@ -2263,28 +1909,25 @@ class MultiGridEnv(object):
             sd["prestige_t"] = self.prestige_t.clone()
         if self.ep_return_t is not None:        # episode_info: the running episodes' return accumulators
             sd["ep_return_t"] = self.ep_return_t.clone()
-        if self._params_declared():             # `_gen_grid` names parameters: the table they are read from
+        if self._params.decl:             # `_gen_grid` names parameters: the table they are read from
             sd["params_t"] = self.params_t.clone()
-        if self._levels_on:                     # set_levels: the running episodes' levels, and the seed each env resets to next
+        if self._levels.on:                     # set_levels: the running episodes' levels, and the seed each env resets to next
             sd["episode_level_t"] = self.episode_level.clone()      # (resolved through the bank now: a bank is no part of a checkpoint)
-            sd["level_next_t"] = self._level_next()
+            sd["level_next_t"] = self._levels.next()
         sd["version"] = torch.tensor(STATE_DICT_VERSION)
         return sd
-
-    def _params_declared(self):
-        return bool(self._param_decl)
 
     def load_state_dict(self, sd):
         want = set(self._STATE_KEYS) | {"version"} | ({"prestige_t"} if self.prestige_t is not None else set())
         want |= {"ep_return_t"} if self.ep_return_t is not None else set()
-        want |= {"params_t"} if self._params_declared() else set()
+        want |= {"params_t"} if self._params.decl else set()
         levels = {"episode_level_t", "level_next_t"} & set(sd.keys())       # (optional: a checkpoint without them loads as before)
         if levels and len(levels) != 2:
             raise KeyError("load_state_dict: 'episode_level_t' and 'level_next_t' come together")
         if levels:
             if tuple(sd["level_next_t"].shape) != (self.batch_size,):
                 raise ValueError("load_state_dict: level_next_t has shape %s, expected %s" % (tuple(sd["level_next_t"].shape), (self.batch_size,)))
-            self._enable_levels()
+            self._levels.enable()
         want |= levels
         if set(sd.keys()) != want:
             raise KeyError("load_state_dict: expected exactly the keys %s, got %s (a checkpoint without "

@@ -155,9 +155,9 @@ Recording = collections.namedtuple("Recording", "template ops sym late")
 
 class GenRecorder(object):
     """All state and logic of recording one env's `_gen_grid`.  From the env it takes `width`, `height`, `obj_reg`,
-    `agent_spawn_kwargs`, the `_gen_grid` callable, `_place_region`, `_reject_table` and `_param_column` (the env owns the
-    device table), and it leaves `env.grid`.  The env's `_rand_int` / `_param` / `_fork` / `place_obj` delegate here while
-    `active`; `MultiGrid` reports its static edits here."""
+    `agent_spawn_kwargs`, the `_gen_grid` callable, `_place_region`, `_reject_table` and `_param_column` (the env's ParamTable,
+    gen_params.py, owns the device table), and it leaves `env.grid`.  The env's `_rand_int` / `_param` / `_fork` / `place_obj`
+    delegate here while `active`; `MultiGrid` reports its static edits here."""
 
     width = property(lambda self: self.env.width)
     height = property(lambda self: self.env.height)

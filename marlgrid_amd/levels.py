@@ -1,0 +1,212 @@
+"""Replayable levels, host side: `LevelBank` — freshly seeded generators on one device — and `EnvLevels`, what a MultiGridEnv
+keeps for `set_levels` (the env holds one as `env._levels`, as it holds the recorder as `env._gen`): which bank its envs read,
+the slot of each, and the mg_level_apply launch in front of every reset and step.  The kernels are csrc/mg_levels.hip."""
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N, per_env as P
+
+
+class LevelBank(object):
+    """Replayable levels: L freshly seeded generators on one device.  A level is a seed; playing it is the reference's
+    `env.seed(s); env.reset()` (base.py:371-374, 402-416) — layout, agent placement and every later draw of the episode come
+    from a generator seeded with s.  `mt` (L, 624), `pos` (L,), `head` (L, 16): what mg_mt_seed leaves per env; `seeds` (L,)
+    int64, -1 = empty slot.  `seeds_or_capacity`: an int — that many empty slots — or the slots' seeds (-1: empty).
+    An env is pointed at slots with `env.set_levels(bank, ids)` and takes a copy of its slot's generator at its next reset;
+    `assign` replaces levels.  Seeds are hashed and the generators seeded on the device (mg_level_seed)."""
+
+    def __init__(self, seeds_or_capacity, device=None, _dry=False):
+        self._dry = bool(_dry)
+        self._replicas = {}         # device -> the copy of this bank a shard on that device reads (sharding._Shards.set_levels)
+        self._readers = {}          # streams that read this bank's rows (an env's mg_level_apply): what `assign` orders itself with
+        self.launches = 0
+        first = None
+        if isinstance(seeds_or_capacity, (int, np.integer)) and not isinstance(seeds_or_capacity, bool):
+            L = int(seeds_or_capacity)
+        else:
+            first = seeds_or_capacity
+            L = int(first.shape[0]) if hasattr(first, "shape") and len(first.shape) == 1 else len(first)
+        if L < 1:
+            raise ValueError("LevelBank: at least one slot")
+        self.capacity = L
+        if self._dry:
+            self.device = None
+            self.seeds = np.full(L, -1, np.int64)
+        else:
+            import torch
+            self.device = torch.device(device if device is not None else "cuda")
+            if self.device.type != "cuda":
+                raise RuntimeError("marlgrid_amd runs on HIP devices only (got %r)" % (device,))
+            if self.device.index is None:
+                self.device = torch.device("cuda", torch.cuda.current_device())
+            self._lib = N.lib()
+            with torch.cuda.device(self.device):
+                self.mt = torch.zeros((L, N.MT_N), dtype=torch.int32, device=self.device)
+                self.pos = torch.zeros((L,), dtype=torch.int32, device=self.device)
+                self.head = torch.zeros((L, N.MT_HEAD), dtype=torch.int32, device=self.device)
+                self.seeds = torch.full((L,), -1, dtype=torch.int64, device=self.device)
+        if first is not None:
+            self.assign(None, first)
+
+    def __len__(self):
+        return self.capacity
+
+    def assign(self, slots, seeds):
+        """Put `seeds` (k,) into `slots` (k,) — None: slots 0 .. k-1 —, in stream order: the envs pointed at a slot play its new
+        level from their next reset on.  -1 empties a slot (its envs run free).  Device int64 tensors: one launch, nothing is
+        read back, and two entries naming one slot are the caller's error; host values are checked (ValueError for a slot
+        outside the bank, a seed < -1, a slot named twice)."""
+        L = self.capacity
+        if P.on_device(seeds, self.device) and (slots is None or P.on_device(slots, self.device)):
+            if seeds.dim() != 1 or (slots is not None and tuple(slots.shape) != tuple(seeds.shape)):
+                raise ValueError("LevelBank.assign: slots and seeds of one shape (k,)")
+        else:
+            seeds = P.host_ints(seeds, "LevelBank.assign(seeds=)").reshape(-1)
+            if seeds.size and seeds.min() < -1:
+                raise ValueError("LevelBank.assign(seeds=): a seed is >= 0, or -1 for none (got %d)" % seeds.min())
+            if slots is not None:
+                slots = P.host_ints(slots, "LevelBank.assign(slots=)").reshape(-1)
+                if slots.shape != seeds.shape:
+                    raise ValueError("LevelBank.assign: slots and seeds of one shape (k,)")
+                if slots.size and (slots.min() < 0 or slots.max() >= L):
+                    raise ValueError("LevelBank.assign: slots outside 0..%d" % (L - 1))
+                if len(np.unique(slots)) != slots.size:
+                    raise ValueError("LevelBank.assign: a slot is named twice")
+            elif seeds.size > L:
+                raise ValueError("LevelBank.assign: %d seeds for %d slots" % (seeds.size, L))
+            if self._dry:
+                self.seeds[np.arange(seeds.size) if slots is None else slots] = seeds
+                return
+        self._seed_rows(seeds, slots, None)
+        for rep in self._replicas.values():
+            rep.assign(slots, seeds)
+
+    def _seed_rows(self, seeds, slots, mask):
+        """mg_level_seed on torch's current stream of the bank's device, ordered against the streams that read the bank"""
+        import torch
+        with torch.cuda.device(self.device):
+            def dev(v):
+                if v is None:
+                    return None
+                v = v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v))
+                return v.to(device=self.device, dtype=torch.int64).contiguous()
+            seeds, slots = dev(seeds), dev(slots)
+            cur = torch.cuda.current_stream(self.device)
+            others = [r for r in self._readers.values() if r != cur]
+            for r in others:                        # rows an earlier step's launch still reads are not overwritten under it
+                cur.wait_event(r.record_event())
+            N.check(self._lib.mg_level_seed(int(seeds.shape[0]), seeds.data_ptr(), None if slots is None else slots.data_ptr(),
+                                            None if mask is None else mask.data_ptr(), self.capacity, self.mt.data_ptr(),
+                                            self.pos.data_ptr(), self.head.data_ptr(), self.seeds.data_ptr(), C.c_void_p(cur.cuda_stream)))
+            self.launches += 1
+            if others:
+                ev = cur.record_event()
+                for r in others:
+                    r.wait_event(ev)
+
+    def replica(self, device, streams=()):
+        """this bank's levels on `device`, for shards that live there and step on `streams`: seeded there from `seeds` (one
+        launch, no generator crosses devices) and kept up to date by `assign`"""
+        import torch
+        device = torch.device(device)
+        rep = self._replicas.get(device)
+        if rep is None:
+            rep = LevelBank(self.capacity, device)
+            for s in streams:
+                rep._readers[s.cuda_stream] = s
+            with torch.cuda.device(device):
+                rep._seed_rows(self.seeds.to(device), None, None)
+            self._replicas[device] = rep
+        for s in streams:
+            rep._readers[s.cuda_stream] = s
+        return rep
+
+
+class EnvLevels(object):
+    """The env side of replayable levels — `env._levels`; MultiGridEnv.set_levels, whose docstring is the contract, delegates
+    here.  Nothing is allocated or launched until `set` is first called."""
+
+    def __init__(self, env):
+        self.env = env
+        self.on = False             # set_levels was called: every reset and step is preceded by mg_level_apply
+        self.launches = 0           # ... how many of them there were
+        self.bank = self.own_bank = None    # the one bank the batch reads now; the env's own (the seeds form: row b is env b's)
+        self.level_of_env = None    # (B,) int64: each env's slot of `bank`, -1: free-running
+
+    def enable(self):
+        """the tensors of set_levels, made at its first call: an env that never calls it allocates and launches nothing"""
+        env = self.env
+        if self.on:
+            return
+        if env.auto_reset_mode == "same_step":
+            raise ValueError("set_levels: with auto_reset=True a same-step reset happens inside the launch that ends the episode, "
+                             "where no level can be handed over; construct the env with auto_reset='next_step' (or False)")
+        self.on = True
+        if env._dry:
+            self.level_of_env = np.full(env.batch_size, -1, np.int64)
+            return
+        import torch
+        B, dev = env.batch_size, env.device
+        self.level_of_env = torch.full((B,), -1, dtype=torch.int64, device=dev)
+        for r in env._ring:
+            r["level"] = torch.full((B,), -1, dtype=torch.int64, device=dev)
+            if "info" in r:
+                r["info"]["level"] = r["level"]
+
+    def set(self, bank=None, ids=None, seeds=None, env_mask=None, env_ids=None):
+        env, B = self.env, self.env.batch_size
+        dev = None if env._dry else env.device
+        if (bank is None) == (seeds is None) or (bank is not None and ids is None) or (seeds is not None and ids is not None):
+            raise ValueError("set_levels: either (bank, ids) or seeds=")
+        mask, eids = P.select(B, dev, env_mask, env_ids, "set_levels")
+        self.enable()
+        if bank is not None:
+            if not isinstance(bank, LevelBank):
+                raise ValueError("set_levels: bank must be a LevelBank")
+            if dev is not None and bank.device != dev:
+                raise ValueError("set_levels: the bank lives on %s, the env on %s (env.level_bank(...) makes one here)" % (bank.device, dev))
+            v = P.values(ids, -1, bank.capacity, B, eids, dev, "set_levels(ids=)", "[-1, %d)" % bank.capacity)
+        else:       # (device tensors pass: mg_level_seed guards the range)
+            v = P.values(seeds, -1, None, B, eids, dev, "set_levels(seeds=)", "[-1, 2**63)")
+            if self.own_bank is None:
+                self.own_bank = env.level_bank(B)
+            bank = self.own_bank
+        if bank is not self.bank:
+            if (mask is not None or eids is not None) and self.bank is not None:
+                raise ValueError("set_levels: the envs of one batch read one bank at a time; change to another bank (or between a "
+                                 "bank and seeds=) with a call for every env")
+            self.bank = bank
+            if bank is self.own_bank and dev is None:       # row b is env b's: whether it plays a level is whether its row is filled
+                self.level_of_env[:] = np.arange(B)
+                bank.seeds[:] = -1
+            elif bank is self.own_bank:
+                import torch
+                torch.arange(B, out=self.level_of_env)
+                bank.seeds.fill_(-1)
+        if bank is self.own_bank and dev is not None:       # (the rows' generators are seeded with them: one launch)
+            bank._readers.update(env._launch_streams)
+            bank._seed_rows(v if v.ndim else v.expand(B if eids is None else eids.shape[0]).contiguous(), eids, mask)
+        else:
+            P.write(bank.seeds if bank is self.own_bank else self.level_of_env, v, mask, eids)
+
+    def apply(self, rule, mask_ptr, stream):
+        """mg_level_apply in front of a reset or a step: the envs the rule selects take their level's generator; every env's
+        running level goes to the current buffer set.  Nothing unless set_levels was ever called."""
+        env, bank = self.env, self.bank
+        if not self.on or env._dry or bank is None:
+            return
+        bank._readers.update(env._launch_streams)
+        N.check(env._lib.mg_level_apply(C.byref(env._cfg), C.byref(env._state), rule, mask_ptr, self.level_of_env.data_ptr(),
+                                        bank.capacity, bank.mt.data_ptr(), bank.pos.data_ptr(), bank.head.data_ptr(), bank.seeds.data_ptr(),
+                                        env.episode_level.data_ptr(), env._ring[env._ring_i]["level"].data_ptr(), stream))
+        self.launches += 1
+
+    def next(self):
+        """(B,) int64: the seed each env's next reset will use, resolved through the bank (-1: free-running)"""
+        import torch
+        bank, lv = self.bank, self.level_of_env
+        if bank is None:
+            return torch.full_like(lv, -1)
+        ok = (lv >= 0) & (lv < bank.capacity)
+        return torch.where(ok, bank.seeds[lv.clamp(0, bank.capacity - 1)], torch.full_like(lv, -1))

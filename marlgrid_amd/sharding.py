@@ -101,30 +101,19 @@ def split_state_dict(sd, ranges):
     return [dict({k: v[lo:hi] for k, v in sd.items() if k != "version"}, version=sd["version"].clone()) for lo, hi in ranges]
 
 
-def split_params(ranges, env_mask=None, env_ids=None, **values):
+def split_params(ranges, env_mask=None, env_ids=None, _who="set_params", **values):
     """`MultiGridEnv.set_params` arguments in GLOBAL env order -> one dict of keyword arguments per (lo, hi) of `ranges` (None
     for a shard that none of `env_ids` falls into): rows lo .. hi of `env_mask` and of every per-env value, `env_ids` of the
     shard rebased to it together with their values.  `env_ids` are read on the host (a device tensor is copied: a host
-    sync); masks and values may stay on their device — they are only sliced."""
+    sync); masks and values may stay on their device — they are only sliced.  `_who`: the caller's name in the messages."""
     import numpy as np
+    from . import per_env as P
     ranges = [(int(lo), int(hi)) for lo, hi in ranges]
     B = ranges[-1][1]
-    if env_mask is not None and env_ids is not None:
-        raise ValueError("set_params: env_mask or env_ids, not both")
-    if env_mask is not None and tuple(env_mask.shape if hasattr(env_mask, "shape") else np.shape(env_mask)) != (B,):
-        raise ValueError("env_mask must have shape (batch_size,)")
-    ids = None
-    if env_ids is not None:
-        ids = np.asarray(env_ids.cpu() if hasattr(env_ids, "cpu") else env_ids).astype(np.int64).reshape(-1)
-        if ids.size and (ids.min() < 0 or ids.max() >= B):
-            raise ValueError("set_params: env_ids outside 0..%d" % (B - 1))
-
-    def shape(v):
-        return tuple(v.shape) if hasattr(v, "shape") else np.shape(v)
+    P.check_selectors(B, env_mask, env_ids, _who)
+    ids = None if env_ids is None else P.host_ids(env_ids, B, _who, any_number=True)
     for name, v in values.items():
-        want = (B,) if ids is None else (len(ids),)
-        if shape(v) not in ((), want, (B,)):
-            raise ValueError("set_params(%s=): an int or one value per env, shape %s; got %s" % (name, want, shape(v)))
+        P.check_value_shape(P.shape_of(v), B, None if ids is None else len(ids), "%s(%s=)" % (_who, name))
     out = []
     for lo, hi in ranges:
         kw = {}
@@ -138,9 +127,9 @@ def split_params(ranges, env_mask=None, env_ids=None, **values):
                 continue
             kw["env_ids"] = ids[sel] - lo
         for name, v in values.items():
-            if shape(v) == ():
+            if P.shape_of(v) == ():
                 kw[name] = v
-            elif ids is not None and shape(v) == (len(ids),):
+            elif ids is not None and P.shape_of(v) == (len(ids),):
                 v = v if hasattr(v, "shape") else np.asarray(v)
                 kw[name] = v[sel] if isinstance(v, np.ndarray) else v[sel.tolist()]
             else:
@@ -155,11 +144,7 @@ def split_levels(ranges, ids=None, seeds=None, env_mask=None, env_ids=None):
     `seeds`, an int or one value per env.  The bank is not part of it (a shard reads a replica on its own device)."""
     if (ids is None) == (seeds is None):
         raise ValueError("set_levels: either (bank, ids) or seeds=")
-    name, v = ("ids", ids) if ids is not None else ("seeds", seeds)
-    try:
-        return split_params(ranges, env_mask=env_mask, env_ids=env_ids, **{name: v})
-    except ValueError as e:
-        raise ValueError(str(e).replace("set_params", "set_levels")) from None
+    return split_params(ranges, env_mask, env_ids, "set_levels", **({"ids": ids} if ids is not None else {"seeds": seeds}))
 
 
 def max_over_ranks(value, device=None):
@@ -255,7 +240,7 @@ class _Shards(object):
                 reps[k] = bank.replica(env.device, [s for s, e in zip(self.streams, self.envs) if e.device == env.device])
 
         def one(k, env):
-            env._enable_levels()        # (every shard, selected or not: a checkpoint has the level keys in every shard or in none)
+            env._levels.enable()        # (every shard, selected or not: a checkpoint has the level keys in every shard or in none)
             if parts[k] is not None:
                 env.set_levels(bank=reps[k] if bank is not None and reps[k] is not None else bank, **parts[k])
         self._each(one)

@@ -80,6 +80,8 @@ extern "C" {
 #define MG_GEN_NEG 0x20000000     /*   set: const - draw[r]; clear: const + draw[r] */
 #define MG_GEN_DRAW_SHIFT 16      /*   r = (operand >> 16) & 7; const = (int16_t)(operand & 0xFFFF) */
 #define MG_GEN_PARAM (-2)         /* MgGenOp.max_tries of a PARAM op: a draw register loaded from the env's row of the parameter table */
+#define MG_GEN_EDITS (-3)         /* MgGenOp.max_tries of an EDITS op: the env's own list of cell edits, applied in order */
+#define MG_GEN_MAX_EDITS 64       /* entries of an env's edit list, at most (MgGenOp.count of an EDITS op) */
 /* the guard of a reset-program op, in the upper bits of MgGenOp.obj (values that were illegal before: ABI 6 still) */
 #define MG_GEN_GUARD 0x40000000   /* the op runs only if lo <= draw[r] <= hi (lo <= hi); else it is skipped entirely */
 #define MG_GEN_GUARD_DRAW_SHIFT 24 /*   r = (obj >> 24) & 7 */
@@ -233,6 +235,14 @@ typedef struct MgGenOp {
                                    * declared interval (within 0..255).  The clamp makes a table of any bytes safe: no value moves
                                    * a fill or a sampling rectangle outside what was proved for the interval.  Guardable like any
                                    * op.  max_tries == -1 is the RNG draw.
+                                   * max_tries == MG_GEN_EDITS (-3; meaningless before: ABI 6 still): EDITS, the env's own list of
+                                   * cell edits — `count` = K entries (1 .. MG_GEN_MAX_EDITS) of uint8_t edits[B][K][4] behind the
+                                   * parameter table (MgGenProgram.template_grid), an entry being (x, y, obj, on).  For env b and
+                                   * k = 0 .. K-1 in order: if on != 0, x < W, y < H and obj < n_obj, cell (x, y) becomes obj (0
+                                   * empties it) — what a static edit (max_tries == 0) does to one cell; a later entry wins.  Any
+                                   * other entry is ignored: no error, no write outside the env's grid slice, whatever bytes the
+                                   * table holds.  No draw register, no RNG word; obj's low byte, the rectangle and reject are
+                                   * unused (0, 0, -1); guardable like any op.
                                    * `count` of a placement may carry MG_GEN_SYM too (`const +- draw[r]`, illegal before): evaluated
                                    * per env like the rectangle's operands, below 0 counts as 0; that many consecutive place_obj
                                    * calls, consuming the same RNG words in the same order.
@@ -256,7 +266,11 @@ typedef struct MgGenProgram {
     const uint8_t* template_grid; /* device, [cells_stride].  A program that holds a PARAM op (MG_GEN_PARAM) is followed DIRECTLY by
                                    * the parameter table: uint8_t params[B][MG_GEN_DRAWS] at template_grid + cells_stride, row = env,
                                    * column = the op's y0; read at every reset of an env (a change takes effect at the env's next
-                                   * reset).  Every other program is the bytes it was and needs no tail.  (Not behind `ops`: the fused
+                                   * reset).  A program that holds an EDITS op (MG_GEN_EDITS) has, whether it holds a PARAM op or not,
+                                   * that table's B * MG_GEN_DRAWS bytes and DIRECTLY behind them uint8_t edits[B][K][4] (K = the op's
+                                   * count) at template_grid + cells_stride + B * MG_GEN_DRAWS: rows of 4-byte aligned entries
+                                   * (x, y, obj, on), read at every reset of an env like the parameters.
+                                   * Every other program is the bytes it was and needs no tail.  (Not behind `ops`: the fused
                                    * kernel reads programs of at most 32 ops from an LDS copy; template_grid is read in place.) */
     int32_t n_ops;
     const MgGenOp* ops;           /* DEVICE, [n_ops]: placements and late static edits, in `_gen_grid` order — upstream's `_gen_grid`
@@ -313,6 +327,19 @@ int32_t mg_level_apply(const MgConfig* cfg, const MgState* st, int32_t rule, con
                        const int64_t* level_of_env, int32_t n_slots, const uint32_t* bank_mt, const int32_t* bank_pos,
                        const uint32_t* bank_head, const int64_t* bank_seed, int64_t* episode_level, int64_t* out_level,
                        void* stream);
+/* mg_level_apply_rows: mg_level_apply for a bank whose levels also carry a parameter row and an edit list.  Everything above,
+ * and for every selected env that takes a slot (>= 0, filled) the slot's rows are copied over the env's, in the same launch, by
+ * the wave that copies the generator: bank_params uint8 [L][MG_GEN_DRAWS] -> env_params uint8 [B][MG_GEN_DRAWS] and bank_edits
+ * uint8 [L][K][4] -> env_edits uint8 [B][K][4] — the env's tables are the ones behind its reset programs' template
+ * (MgGenProgram.template_grid), so the reset in the launch that follows reads the level's rows, and the env's rows afterwards
+ * show what the running episode was built from.  Free-running and unselected envs keep their rows.  A pair (bank_*, env_*) is
+ * given whole or NULL — NULL: that part is not copied —; 1 <= K <= MG_GEN_MAX_EDITS with an edit pair, else 0; the four
+ * pointers 4-byte aligned.  All device memory, caller-owned. */
+int32_t mg_level_apply_rows(const MgConfig* cfg, const MgState* st, int32_t rule, const uint8_t* env_mask,
+                            const int64_t* level_of_env, int32_t n_slots, const uint32_t* bank_mt, const int32_t* bank_pos,
+                            const uint32_t* bank_head, const int64_t* bank_seed, int64_t* episode_level, int64_t* out_level,
+                            const uint8_t* bank_params, const uint8_t* bank_edits, int32_t K, uint8_t* env_params,
+                            uint8_t* env_edits, void* stream);
 
 /* actions: device [B][n_agents], element size `action_bytes` in {1,4,8} (little-endian ints).
  * rewards: device float32 [B][n_agents].  Sets st->done[b].

@@ -12,6 +12,8 @@ ABI_VERSION = 6
 # `_rand_int` draws of a reset program (MG_GEN_* in the C header): an operand with GEN_SYM is `const +- draw[r]`
 GEN_DRAWS, GEN_SYM, GEN_NEG, GEN_DRAW_SHIFT = 8, 0x40000000, 0x20000000, 16
 GEN_PARAM = -2              # GenOp.max_tries of a PARAM op (MG_GEN_PARAM): draw[obj] = clamp(params[env][y0], x0, x1 - 1), no RNG word
+GEN_EDITS = -3              # GenOp.max_tries of an EDITS op (MG_GEN_EDITS): `count` entries (x, y, obj, on) of the env's edit list
+GEN_MAX_EDITS = 64          # ... at most (MG_GEN_MAX_EDITS)
 # ... and the guard of an op, in the upper bits of GenOp.obj (MG_GEN_GUARD*): the op runs only where lo <= draw[r] <= hi
 GEN_GUARD, GEN_GUARD_DRAW_SHIFT, GEN_GUARD_HI_SHIFT, GEN_GUARD_LO_SHIFT = 0x40000000, 24, 16, 8
 
@@ -142,7 +144,7 @@ SYMBOLS = ["mg_abi_version", "mg_struct_sizes", "mg_host_flag_alloc", "mg_host_f
            "mg_step_render_delta", "mg_step_render_delta_ex",
            "mg_spec_info_struct_size", "mg_render_specialize", "mg_step_render_spec", "mg_render_obs_spec",
            "mg_render_spec_release", "mg_rtc_source",
-           "mg_level_seed", "mg_level_apply"]
+           "mg_level_seed", "mg_level_apply", "mg_level_apply_rows"]
 
 _lib = None
 _path = LIB_PATH
@@ -211,6 +213,8 @@ def lib():
     L.mg_level_seed.argtypes = [i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     # (cfg, st, rule, env_mask, level_of_env, n_slots, bank_mt, bank_pos, bank_head, bank_seed, episode_level, out_level, stream)
     L.mg_level_apply.argtypes = [C.POINTER(Config), C.POINTER(State), i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    # (... out_level, bank_params, bank_edits, K, env_params, env_edits, stream)
+    L.mg_level_apply_rows.argtypes = [C.POINTER(Config), C.POINTER(State), i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.mg_reset.argtypes = [C.POINTER(Config), C.POINTER(State), C.POINTER(GenProgram), vp, vp]
     L.mg_step.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp]
     L.mg_step_render.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp]

@@ -35,6 +35,7 @@ import numpy as np
 from . import _native as N
 from . import per_env, rendering, seeding, spaces
 from .agents import GridAgentInterface
+from .gen_edits import EditTable
 from .gen_params import ParamTable
 from .gen_recorder import GenDraw, GenRecorder, _NO_BRANCH, _any_draw, _gen_add, _trace, decode_program, pack_program
 from .levels import EnvLevels, LevelBank
@@ -439,7 +440,7 @@ class MultiGridEnv(object):
                  reward_decay=True, seed=1337, respawn=False, ghost_mode=True, agent_spawn_kwargs={},
                  batch_size=1, device=None, seeds=None, auto_reset=False, strict=True, obs_buffers=2,
                  fused_step=True, place_obs=True, encode_in_step=False, obs_format="image", episode_info=False,
-                 obs_delta="auto", specialize=False, specialize_cache=None, _dry=False):
+                 obs_delta="auto", specialize=False, specialize_cache=None, level_edits=0, _dry=False):
         if grid_size is not None:
             assert width is None and height is None
             width, height = grid_size, grid_size
@@ -565,6 +566,11 @@ class MultiGridEnv(object):
         self._prog_cache = {}
         self._params = ParamTable(self)     # the per-env parameters of `_gen_grid` (gen_params.py)
         self._levels = EnvLevels(self)      # replayable levels (levels.py): nothing is allocated or launched until set_levels
+        # level_edits=K (0..64): every env holds a list of K cell edits (x, y, kind, on) that its every reset applies behind
+        # what `_gen_grid` laid out and before the agents are placed (an EDITS op at the end of the reset program; set_edits).
+        # 0: no table, no op — recordings, programs and launches are what they were
+        self._edits = EditTable(self, level_edits)
+        self.level_edits = self._edits.K
         self._spec_ctor = None
         self._spec_last = None
         self._probe = None
@@ -581,6 +587,7 @@ class MultiGridEnv(object):
                 self.device = torch.device("cuda", torch.cuda.current_device())
             self._lib = N.lib()
             self._alloc_state()
+        self._edits.alloc()
         self._seeds_arg = seeds
         self.seed(seed=seed)
         self.reset()
@@ -1018,10 +1025,35 @@ class MultiGridEnv(object):
         step launch, a next-step reset —: the running episode is untouched."""
         self._params.set(env_mask, env_ids, **values)
 
+    # ---- per-env cell edits: the last op of the reset program -------------------------------------------------------------
+    edits_t = property(lambda self: self._edits.table)      # (B, K, 4) uint8 entries (x, y, kind, on); None at level_edits=0
+
+    @_on_device
+    def edit_key(self, obj):
+        """the kind id of an object instance for an edit entry (None: 0, an empty cell).  A kind seen for the first time is
+        registered and the device tables are brought up to date: the id is valid in the launch that next resets."""
+        key = self.obj_reg.get_key(obj)
+        self._sync_tables()
+        return key
+
+    @_on_device
+    def set_edits(self, edits, env_mask=None, env_ids=None):
+        """Set the edit lists of a `level_edits=K` env: `edits` is (K', 4) entries `(x, y, kind, on)` for every selected env —
+        all, those of `env_mask` ((B,) bool) or those listed in `env_ids` — or one list per selected env, (B, K', 4) or with
+        `env_ids` (k, K', 4); K' <= K, the slots from K' on are switched off.  An entry that is on writes `kind`
+        (`env.edit_key(obj)`; 0 empties the cell) into cell (x, y) as `put_obj` / `grid.set` at the end of `_gen_grid` would,
+        in list order.  Host values are checked (ValueError: x >= width, y >= height, a kind that is not registered, K' > K);
+        a device tensor is written in stream order with nothing read back, and the device ignores an entry outside the grid
+        or of an unknown kind.  A list takes effect when its env next resets — reset(), the reset inside a step launch, a
+        next-step reset —: the running episode is untouched."""
+        self._edits.set(edits, env_mask, env_ids)
+
     # ---- replayable levels ----------------------------------------------------------------------------------------------
-    def level_bank(self, seeds_or_capacity):
-        """a LevelBank on this env's device"""
-        return LevelBank(seeds_or_capacity, None if self._dry else self.device, _dry=self._dry)
+    def level_bank(self, seeds_or_capacity, full=False):
+        """a LevelBank on this env's device.  `full`: its slots also hold a row of this env's parameters (`bank.params`, at the
+        declared defaults) and a list of `level_edits` cell edits (`bank.edits`, all off) — a level is (seed, parameters,
+        edits), set with `bank.assign(slots, seeds, params=, edits=)` and taken whole by an env at its reset"""
+        return LevelBank(seeds_or_capacity, None if self._dry else self.device, _dry=self._dry, env=self if full else None)
 
     @_on_device
     def set_levels(self, bank=None, ids=None, seeds=None, env_mask=None, env_ids=None):
@@ -1400,7 +1432,7 @@ class MultiGridEnv(object):
         key = (template.tobytes(), tuple(ops))
         # a program with a PARAM op reads the env's parameter table right behind its template: all such programs of this env
         # share ONE buffer — template, then table —, whose head is rewritten (in stream order) when the template changes
-        has_param = any(op.is_param for op in ops)
+        has_param = any(op.is_param or op.is_edits for op in ops)      # (... or an EDITS op: the edit table behind that one)
         if has_param and self._params.tpl != key[0]:
             t = np.zeros(self.cells_stride, np.uint8)
             t[:self.width * self.height] = template.reshape(-1)
@@ -1911,6 +1943,8 @@ class MultiGridEnv(object):
             sd["ep_return_t"] = self.ep_return_t.clone()
         if self._params.decl:             # `_gen_grid` names parameters: the table they are read from
             sd["params_t"] = self.params_t.clone()
+        if self.level_edits:              # the envs' edit lists
+            sd["edits_t"] = self.edits_t.clone()
         if self._levels.on:                     # set_levels: the running episodes' levels, and the seed each env resets to next
             sd["episode_level_t"] = self.episode_level.clone()      # (resolved through the bank now: a bank is no part of a checkpoint)
             sd["level_next_t"] = self._levels.next()
@@ -1921,6 +1955,7 @@ class MultiGridEnv(object):
         want = set(self._STATE_KEYS) | {"version"} | ({"prestige_t"} if self.prestige_t is not None else set())
         want |= {"ep_return_t"} if self.ep_return_t is not None else set()
         want |= {"params_t"} if self._params.decl else set()
+        want |= {"edits_t"} if self.level_edits else set()
         levels = {"episode_level_t", "level_next_t"} & set(sd.keys())       # (optional: a checkpoint without them loads as before)
         if levels and len(levels) != 2:
             raise KeyError("load_state_dict: 'episode_level_t' and 'level_next_t' come together")

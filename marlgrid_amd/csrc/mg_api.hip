@@ -166,6 +166,30 @@ int32_t mg_level_apply(const MgConfig* cfg, const MgState* st, int32_t rule, con
                                      episode_level, out_level, (hipStream_t)stream));
 }
 
+int32_t mg_level_apply_rows(const MgConfig* cfg, const MgState* st, int32_t rule, const uint8_t* env_mask, const int64_t* level_of_env,
+                            int32_t n_slots, const uint32_t* bank_mt, const int32_t* bank_pos, const uint32_t* bank_head,
+                            const int64_t* bank_seed, int64_t* episode_level, int64_t* out_level, const uint8_t* bank_params,
+                            const uint8_t* bank_edits, int32_t K, uint8_t* env_params, uint8_t* env_edits, void* stream) {
+    if (!cfg || cfg->B < 0 || cfg->n_agents < 1 || cfg->n_agents > MG_MAX_AGENTS) return MG_E_ARG;
+    const int e = check_state(st);
+    if (e) return e;
+    if (rule != MG_LEVEL_PUBLISH && rule != MG_LEVEL_PENDING && rule != MG_LEVEL_MASK) return MG_E_ARG;
+    if (n_slots < 0 || !episode_level) return MG_E_ARG;
+    if (rule != MG_LEVEL_PUBLISH && (!level_of_env || (n_slots > 0 && (!bank_mt || !bank_pos || !bank_head || !bank_seed)))) return MG_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(bank_mt) | reinterpret_cast<uintptr_t>(bank_head) | reinterpret_cast<uintptr_t>(st->mt) |
+         reinterpret_cast<uintptr_t>(st->mt_head)) & 15)
+        return MG_E_ARG;
+    // the rows: a pair comes whole or not at all; an edit pair with 1 <= K <= MG_GEN_MAX_EDITS; 32-bit traffic
+    if (!bank_params != !env_params || !bank_edits != !env_edits) return MG_E_ARG;
+    if (bank_edits ? (K < 1 || K > MG_GEN_MAX_EDITS) : K != 0) return MG_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(bank_params) | reinterpret_cast<uintptr_t>(env_params) | reinterpret_cast<uintptr_t>(bank_edits) |
+         reinterpret_cast<uintptr_t>(env_edits)) & 3)
+        return MG_E_ARG;
+    return rc(mg::launch_level_apply_rows(*cfg, *st, rule, env_mask, level_of_env, n_slots, bank_mt, bank_pos, bank_head, bank_seed,
+                                          episode_level, out_level, bank_params, bank_edits, K, env_params, env_edits,
+                                          (hipStream_t)stream));
+}
+
 int32_t mg_episode_struct_size(void) { return (int32_t)sizeof(MgEpisode); }
 
 int32_t mg_step_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,

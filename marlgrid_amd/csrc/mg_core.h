@@ -507,6 +507,24 @@ MG_HD int reset_env(const MgConfig& cfg, const MgState& st, const MgGenProgram& 
         MgGenOp op = prog.ops[o];
         // a branch of `_gen_grid` this env's draws did not take: no RNG word, no write, no error, a draw register as it was
         if (gen_skipped(op.obj, draws)) continue;
+        if (op.max_tries == MG_GEN_EDITS) {
+            // the env's own list of cell edits, `count` entries (x, y, obj, on) of the table behind the parameter table: what a
+            // static put_obj / grid.set fill op does to ONE cell, in list order (a later entry wins).  Whatever bytes the table
+            // holds: an entry that is off, outside the grid or names a kind without a descriptor is ignored — no error, no
+            // byte outside the env's grid slice.  No draw register, no RNG word.
+            // (the row's address is made here, from `b` as it is now, like the PARAM row's; one 32-bit load per entry)
+            const uint32_t K = (uint32_t)(op.count < 0 ? 0 : op.count > MG_GEN_MAX_EDITS ? MG_GEN_MAX_EDITS : op.count);
+            const uint8_t* row = prog.template_grid + (size_t)cfg.cells_stride + (size_t)cfg.B * MG_GEN_DRAWS
+                               + (size_t)(keep_packed((uint32_t)b) * K) * 4u;
+            for (uint32_t k = 0; k < K; k++) {
+                const uint32_t e = reinterpret_cast<const uint32_t*>(row)[k];
+                // (y < H, so cell < W * H says x < W: the cell's index is what is compared and what is stored to)
+                const uint32_t y = (e >> 8) & 0xFFu, kind = (e >> 16) & 0xFFu, cell = (e & 0xFFu) * (uint32_t)H + y;
+                if ((e >> 24) != 0 && y < (uint32_t)H && cell < (uint32_t)(cfg.W * H) && kind < (uint32_t)cfg.n_obj)
+                    g[cell] = (uint8_t)kind;
+            }
+            continue;
+        }
         // operands `const +- draw[r]` (branch-free: a plain operand evaluates to itself); a fill or place rectangle with one is
         // clamped to the grid — place_obj's own clamp, base.py:692-695; for a fill: whatever program a caller hands over,
         // nothing is written outside the env's grid slice

@@ -40,4 +40,8 @@ hipError_t launch_level_seed(int n, const int64_t* seeds, const int64_t* slots, 
 hipError_t launch_level_apply(const MgConfig& cfg, const MgState& st, int rule, const uint8_t* mask, const int64_t* level_of_env,
                               int n_slots, const uint32_t* bank_mt, const int32_t* bank_pos, const uint32_t* bank_head,
                               const int64_t* bank_seed, int64_t* episode_level, int64_t* out_level, hipStream_t s);
+hipError_t launch_level_apply_rows(const MgConfig& cfg, const MgState& st, int rule, const uint8_t* mask, const int64_t* level_of_env,
+                                   int n_slots, const uint32_t* bank_mt, const int32_t* bank_pos, const uint32_t* bank_head,
+                                   const int64_t* bank_seed, int64_t* episode_level, int64_t* out_level, const uint8_t* bank_params,
+                                   const uint8_t* bank_edits, int K, uint8_t* env_params, uint8_t* env_edits, hipStream_t s);
 }  // namespace mg

@@ -183,18 +183,41 @@ constexpr int kLevelMtVecs = MG_MT_N * 4 / 16;            // 156: a generator's 
 constexpr int kLevelHeadVecs = MG_MT_HEAD * 4 / 16;       // 4: the 64-byte head
 constexpr int kLevelItems = kLevelMtVecs + kLevelHeadVecs + 1;   // ... and mt_pos
 
+// mg_level_apply_rows: what a level holds besides its generator — the slot's row of the parameter table (MG_GEN_DRAWS bytes)
+// and its K edit entries (4 bytes each) —, and the env's tables they are copied into (the tails of the buffer a reset program's
+// template_grid points into, marlgrid_hip.h).  A null pair: that part is not copied.  Rows of 32-bit words behind 4-byte
+// aligned bases.
+struct LevelRows {
+    const uint32_t* bank_params = nullptr;      // [L][MG_GEN_DRAWS / 4]
+    uint32_t* env_params = nullptr;             // [B][MG_GEN_DRAWS / 4]
+    const uint32_t* bank_edits = nullptr;       // [L][K]
+    uint32_t* env_edits = nullptr;              // [B][K]
+    int K = 0;
+};
+constexpr int kLevelParamWords = MG_GEN_DRAWS / 4;
+
 // Bank row `slot` -> env b's generator, items lane, lane + lanes, ...: 16-byte loads and stores (rows of 2 496 and 64
-// bytes behind 16-byte aligned bases).  A wave calls it with its 64 lanes, the host with (0, 1).
+// bytes behind 16-byte aligned bases).  A wave calls it with its 64 lanes, the host with (0, 1).  With `rows` the slot's
+// parameter row and edit rows are further items of the same loop: 8 + 4 K bytes, a 32-bit word each.
 MG_HD void level_copy(const MgState& st, int b, int slot, const uint32_t* bank_mt, const int32_t* bank_pos, const uint32_t* bank_head,
-                      int lane, int lanes) {
+                      int lane, int lanes, const LevelRows* rows = nullptr) {
     const LevelVec* src_mt = reinterpret_cast<const LevelVec*>(bank_mt + (size_t)slot * MG_MT_N);
     const LevelVec* src_head = reinterpret_cast<const LevelVec*>(bank_head + (size_t)slot * MG_MT_HEAD);
     LevelVec* dst_mt = reinterpret_cast<LevelVec*>(st.mt + (size_t)b * MG_MT_N);
     LevelVec* dst_head = reinterpret_cast<LevelVec*>(st.mt_head + (size_t)b * MG_MT_HEAD);
-    for (int i = lane; i < kLevelItems; i += lanes) {
+    const int K = rows && rows->bank_edits ? rows->K : 0;
+    const int items = kLevelItems + (rows ? kLevelParamWords + K : 0);
+    for (int i = lane; i < items; i += lanes) {
         if (i < kLevelMtVecs) dst_mt[i] = src_mt[i];
         else if (i < kLevelMtVecs + kLevelHeadVecs) dst_head[i - kLevelMtVecs] = src_head[i - kLevelMtVecs];
-        else st.mt_pos[b] = bank_pos[slot];
+        else if (i == kLevelItems - 1) st.mt_pos[b] = bank_pos[slot];
+        else if (i < kLevelItems + kLevelParamWords) {
+            const int w = i - kLevelItems;
+            if (rows->bank_params) rows->env_params[(size_t)b * kLevelParamWords + w] = rows->bank_params[(size_t)slot * kLevelParamWords + w];
+        } else {
+            const int w = i - kLevelItems - kLevelParamWords;
+            rows->env_edits[(size_t)b * K + w] = rows->bank_edits[(size_t)slot * K + w];
+        }
     }
 }
 

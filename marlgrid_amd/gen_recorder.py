@@ -112,6 +112,7 @@ class RecordedOp(collections.namedtuple("RecordedOp", "obj count max_tries x0 y0
                                       0  a fill: `kind` into every cell of the rectangle (a static edit after a placement)
                                      -1  a draw: draw[register] = randint(x0, x1)
                               GEN_PARAM  a parameter load: draw[register] = clamp(params[env][y0], x0, x1 - 1)
+                              GEN_EDITS  the env's own list of `count` cell edits (x, y, kind, on), applied in order
     `obj`: the object kind or the draw register in the low byte; above it the guard of a branch (`_guard_bits`), 0 for none —
     the op runs only in the envs where lo <= draw[r] <= hi.  `count` and the rectangle may be encoded `GenDraw`s (GEN_SYM)."""
     __slots__ = ()
@@ -128,9 +129,14 @@ class RecordedOp(collections.namedtuple("RecordedOp", "obj count max_tries x0 y0
     def fill(cls, key, guard, rect):
         return cls(int(key) | guard, 1, 0, *rect, None)
 
+    @classmethod
+    def edits(cls, K):
+        return cls(0, int(K), N.GEN_EDITS, 0, 0, 0, 0, None)
+
     is_draw = property(lambda self: self.max_tries == -1)
     is_param = property(lambda self: self.max_tries == N.GEN_PARAM)
-    sets_register = property(lambda self: self.max_tries < 0)           # a draw or a PARAM
+    is_edits = property(lambda self: self.max_tries == N.GEN_EDITS)
+    sets_register = property(lambda self: self.max_tries in (-1, N.GEN_PARAM))      # a draw or a PARAM
     is_fill = property(lambda self: self.max_tries == 0)
     is_placement = property(lambda self: self.max_tries > 0)
     kind = register = property(lambda self: self.obj & 0xFF)            # placements and fills / draws and PARAMs
@@ -452,6 +458,9 @@ class GenRecorder(object):
             shared = self.path[-1]["start"]
             prefix = self.ops[:shared]
         env.grid = self.grid = grid             # (the first run's: the template is the same in every run, `_maybe` covers them all)
+        K = getattr(env, "level_edits", 0)
+        if K:       # the env's own cell edits: ONE op behind everything `_gen_grid` recorded, on every path — unguarded
+            merged.append(RecordedOp.edits(K))
         if len(merged) > N.MAX_GEN:
             fills = sum(1 for op in merged if op.is_fill)
             raise NotImplementedError("_gen_grid records %d reset-program ops — %d groups of random placements and %d rectangle "
@@ -474,7 +483,9 @@ def pack_program(ops, width, height, cells_stride, n_objs):
         # the guard of a branch in the upper bits of obj (MG_GEN_GUARD): lo <= hi; the low byte as ever
         g = op.guard
         assert op.guard_bits == 0 or (op.guard_bits & ~0x07FFFF00 == N.GEN_GUARD and g[1] <= g[2])
-        if op.sets_register:        # a `_rand_int` draw, or a PARAM load: obj is its register, y0 a PARAM's table column
+        if op.is_edits:             # the env's edit list: count is K, nothing else is read
+            assert 1 <= op.count <= N.GEN_MAX_EDITS and op.kind == 0 and op.rect == (0, 0, 0, 0) and op.reject is None
+        elif op.sets_register:      # a `_rand_int` draw, or a PARAM load: obj is its register, y0 a PARAM's table column
             assert 0 <= op.register < N.GEN_DRAWS and (op.is_draw or op.is_param)
             assert op.is_draw or (0 <= op.y0 < N.GEN_DRAWS and 0 <= op.x0 < op.x1 <= 256)
         else:

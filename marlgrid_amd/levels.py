@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _native as N, per_env as P
+from . import _native as N, gen_edits, per_env as P
 
 
 class LevelBank(object):
@@ -14,10 +14,19 @@ class LevelBank(object):
     from a generator seeded with s.  `mt` (L, 624), `pos` (L,), `head` (L, 16): what mg_mt_seed leaves per env; `seeds` (L,)
     int64, -1 = empty slot.  `seeds_or_capacity`: an int — that many empty slots — or the slots' seeds (-1: empty).
     An env is pointed at slots with `env.set_levels(bank, ids)` and takes a copy of its slot's generator at its next reset;
-    `assign` replaces levels.  Seeds are hashed and the generators seeded on the device (mg_level_seed)."""
+    `assign` replaces levels.  Seeds are hashed and the generators seeded on the device (mg_level_seed).
 
-    def __init__(self, seeds_or_capacity, device=None, _dry=False):
+    A FULL bank (`env.level_bank(..., full=True)`; `env`: the env it is made from) holds whole levels — seed, parameters, cell
+    edits: `params` (L, MG_GEN_DRAWS) uint8, the columns of the env's `_param` names, every slot at the declared defaults, and
+    `edits` (L, K, 4) uint8 entries (x, y, kind, on), K the env's `level_edits`, all off.  An env that takes a slot's generator
+    takes a copy of the slot's rows over its own in the same launch (mg_level_apply_rows) and its reset reads them."""
+
+    def __init__(self, seeds_or_capacity, device=None, _dry=False, env=None):
         self._dry = bool(_dry)
+        self.full = env is not None
+        self._env = env
+        self.K = env.level_edits if self.full else 0
+        self.params = self.edits = None
         self._replicas = {}         # device -> the copy of this bank a shard on that device reads (sharding._Shards.set_levels)
         self._readers = {}          # streams that read this bank's rows (an env's mg_level_apply): what `assign` orders itself with
         self.launches = 0
@@ -33,6 +42,9 @@ class LevelBank(object):
         if self._dry:
             self.device = None
             self.seeds = np.full(L, -1, np.int64)
+            if self.full:
+                self.params = np.zeros((L, N.GEN_DRAWS), np.uint8)
+                self.edits = np.zeros((L, self.K, 4), np.uint8)
         else:
             import torch
             self.device = torch.device(device if device is not None else "cuda")
@@ -46,18 +58,37 @@ class LevelBank(object):
                 self.pos = torch.zeros((L,), dtype=torch.int32, device=self.device)
                 self.head = torch.zeros((L, N.MT_HEAD), dtype=torch.int32, device=self.device)
                 self.seeds = torch.full((L,), -1, dtype=torch.int64, device=self.device)
+                if self.full:
+                    self.params = torch.zeros((L, N.GEN_DRAWS), dtype=torch.uint8, device=self.device)
+                    self.edits = torch.zeros((L, self.K, 4), dtype=torch.uint8, device=self.device)
+        if self.full:
+            env._ensure_recorded()
+            for d in env._params.decl.values():
+                self.params[:, d["col"]] = d["default"]
         if first is not None:
             self.assign(None, first)
 
     def __len__(self):
         return self.capacity
 
-    def assign(self, slots, seeds):
+    @property
+    def columns(self):
+        """a full bank: parameter name -> its column of `params`"""
+        return {name: d["col"] for name, d in self._env._params.decl.items()} if self.full else {}
+
+    def assign(self, slots, seeds, params=None, edits=None):
         """Put `seeds` (k,) into `slots` (k,) — None: slots 0 .. k-1 —, in stream order: the envs pointed at a slot play its new
         level from their next reset on.  -1 empties a slot (its envs run free).  Device int64 tensors: one launch, nothing is
         read back, and two entries naming one slot are the caller's error; host values are checked (ValueError for a slot
-        outside the bank, a seed < -1, a slot named twice)."""
+        outside the bank, a seed < -1, a slot named twice).
+
+        A full bank also takes the slots' rows: `params` {name: an int or (k,) values} by set_params' rules (host values checked
+        against the parameter's interval, a device tensor clamped to it) and `edits`, (K', 4) for every slot or (k, K', 4), by
+        set_edits' (host entries checked, the slots from K' on switched off).  What is not given stays as the slot has it.  All
+        of it goes in stream order on the ordering of the seeds: no env reads a half-written level."""
         L = self.capacity
+        if (params is not None or edits is not None) and not self.full:
+            raise ValueError("LevelBank.assign(params=, edits=): a bank of seeds holds no rows; env.level_bank(..., full=True) does")
         if P.on_device(seeds, self.device) and (slots is None or P.on_device(slots, self.device)):
             if seeds.dim() != 1 or (slots is not None and tuple(slots.shape) != tuple(seeds.shape)):
                 raise ValueError("LevelBank.assign: slots and seeds of one shape (k,)")
@@ -75,15 +106,50 @@ class LevelBank(object):
                     raise ValueError("LevelBank.assign: a slot is named twice")
             elif seeds.size > L:
                 raise ValueError("LevelBank.assign: %d seeds for %d slots" % (seeds.size, L))
-            if self._dry:
-                self.seeds[np.arange(seeds.size) if slots is None else slots] = seeds
-                return
-        self._seed_rows(seeds, slots, None)
+        k = int(seeds.shape[0])
+        rows = self._rows(k, params, edits)
+        if self._dry:
+            at = np.arange(k) if slots is None else slots
+            self.seeds[at] = seeds
+            self._write_rows(at, rows)
+            return
+        self._seed_rows(seeds, slots, None, rows)
         for rep in self._replicas.values():
-            rep.assign(slots, seeds)
+            rep.assign(slots, seeds, params, edits)
 
-    def _seed_rows(self, seeds, slots, mask):
-        """mg_level_seed on torch's current stream of the bank's device, ordered against the streams that read the bank"""
+    def _rows(self, k, params, edits):
+        """`assign`'s params / edits for k slots, checked: [(column, values)], (K, 4) or (k, K, 4) entries or None"""
+        if not self.full:
+            return None
+        env, dev = self._env, self.device
+        cols = []
+        for name, v in (params or {}).items():
+            d = env._params.decl.get(name)
+            if d is None:
+                raise KeyError("LevelBank.assign: %r is no parameter of the env's _gen_grid (declared: %s)"
+                               % (name, ", ".join(sorted(env._params.decl)) or "none"))
+            cols.append((d["col"], P.values(v, d["lo"], d["hi"], k, None, dev, "LevelBank.assign(%s=)" % name,
+                                            "the parameter's interval [%d, %d)" % (d["lo"], d["hi"]), dtype=np.uint8, wide=False,
+                                            clamp=True)))
+        if edits is not None:
+            if not self.K:
+                raise ValueError("LevelBank.assign(edits=): the env was built without an edit table (level_edits=K)")
+            edits = gen_edits.rows(edits, self.K, k, None, k, env.width, env.height, len(env.obj_reg.objs), dev, "LevelBank.assign")
+        return cols, edits
+
+    def _write_rows(self, at, rows):
+        """the checked rows into slots `at` (an index array / tensor, or a slice)"""
+        if rows is None:
+            return
+        cols, edits = rows
+        for col, v in cols:
+            self.params[at, col] = v
+        if edits is not None:
+            self.edits[at] = edits
+
+    def _seed_rows(self, seeds, slots, mask, rows=None):
+        """mg_level_seed — and the slots' rows — on torch's current stream of the bank's device, ordered against the streams
+        that read the bank"""
         import torch
         with torch.cuda.device(self.device):
             def dev(v):
@@ -100,6 +166,7 @@ class LevelBank(object):
                                             None if mask is None else mask.data_ptr(), self.capacity, self.mt.data_ptr(),
                                             self.pos.data_ptr(), self.head.data_ptr(), self.seeds.data_ptr(), C.c_void_p(cur.cuda_stream)))
             self.launches += 1
+            self._write_rows(slice(0, int(seeds.shape[0])) if slots is None else slots, rows)
             if others:
                 ev = cur.record_event()
                 for r in others:
@@ -112,11 +179,14 @@ class LevelBank(object):
         device = torch.device(device)
         rep = self._replicas.get(device)
         if rep is None:
-            rep = LevelBank(self.capacity, device)
+            rep = LevelBank(self.capacity, device, env=self._env)
             for s in streams:
                 rep._readers[s.cuda_stream] = s
             with torch.cuda.device(device):
-                rep._seed_rows(self.seeds.to(device), None, None)
+                whole = None
+                if self.full:       # (the rows as they are now, every column: no default is put back)
+                    whole = [(c, self.params[:, c].to(device)) for c in range(N.GEN_DRAWS)], self.edits.to(device)
+                rep._seed_rows(self.seeds.to(device), None, None, whole)
             self._replicas[device] = rep
         for s in streams:
             rep._readers[s.cuda_stream] = s
@@ -166,6 +236,9 @@ class EnvLevels(object):
                 raise ValueError("set_levels: bank must be a LevelBank")
             if dev is not None and bank.device != dev:
                 raise ValueError("set_levels: the bank lives on %s, the env on %s (env.level_bank(...) makes one here)" % (bank.device, dev))
+            if bank.full and (bank.K != env.level_edits or set(bank._env._params.decl) != set(env._params.decl)):
+                raise ValueError("set_levels: the full bank was made from an env with other parameters or another level_edits "
+                                 "(env.level_bank(..., full=True) makes one for this env)")
             v = P.values(ids, -1, bank.capacity, B, eids, dev, "set_levels(ids=)", "[-1, %d)" % bank.capacity)
         else:       # (device tensors pass: mg_level_seed guards the range)
             v = P.values(seeds, -1, None, B, eids, dev, "set_levels(seeds=)", "[-1, 2**63)")
@@ -197,9 +270,16 @@ class EnvLevels(object):
         if not self.on or env._dry or bank is None:
             return
         bank._readers.update(env._launch_streams)
-        N.check(env._lib.mg_level_apply(C.byref(env._cfg), C.byref(env._state), rule, mask_ptr, self.level_of_env.data_ptr(),
-                                        bank.capacity, bank.mt.data_ptr(), bank.pos.data_ptr(), bank.head.data_ptr(), bank.seeds.data_ptr(),
-                                        env.episode_level.data_ptr(), env._ring[env._ring_i]["level"].data_ptr(), stream))
+        head = (C.byref(env._cfg), C.byref(env._state), rule, mask_ptr, self.level_of_env.data_ptr(), bank.capacity,
+                bank.mt.data_ptr(), bank.pos.data_ptr(), bank.head.data_ptr(), bank.seeds.data_ptr(), env.episode_level.data_ptr(),
+                env._ring[env._ring_i]["level"].data_ptr())
+        if bank.full:       # the slot's parameter row and edit rows go over the env's in the same launch (a part without a table: null)
+            par, K = env.params_t is not None, env.level_edits
+            N.check(env._lib.mg_level_apply_rows(*head, bank.params.data_ptr() if par else None, bank.edits.data_ptr() if K else None,
+                                                 K, env.params_t.data_ptr() if par else None, env.edits_t.data_ptr() if K else None,
+                                                 stream))
+        else:
+            N.check(env._lib.mg_level_apply(*head, stream))
         self.launches += 1
 
     def next(self):

@@ -62,7 +62,7 @@ def _engine_version():
 def merge_state_dicts(dicts):
     """`MultiGridEnv.state_dict()`s of consecutive slices of a batch -> the state_dict of the whole batch: every tensor
     concatenated along dim 0 in the order given, `version` checked (equal everywhere, and the one this engine reads).  The
-    optional keys (`prestige_t`, `ep_return_t`, `params_t`, and `episode_level_t` with `level_next_t`) are in every dict or in none: anything else raises KeyError.  Pure: no
+    optional keys (`prestige_t`, `ep_return_t`, `params_t`, `edits_t`, and `episode_level_t` with `level_next_t`) are in every dict or in none: anything else raises KeyError.  Pure: no
     device is touched beyond what torch.cat does with the tensors it is given (all on one device)."""
     import torch
     dicts = list(dicts)
@@ -147,6 +147,46 @@ def split_levels(ranges, ids=None, seeds=None, env_mask=None, env_ids=None):
     return split_params(ranges, env_mask, env_ids, "set_levels", **({"ids": ids} if ids is not None else {"seeds": seeds}))
 
 
+def split_edits(ranges, edits, env_mask=None, env_ids=None):
+    """`MultiGridEnv.set_edits` arguments in GLOBAL env order -> one dict of keyword arguments per (lo, hi) of `ranges` (None for
+    a shard that none of `env_ids` falls into), `split_params`' pattern: a (K', 4) list goes to every shard as it is, one list
+    per env — (B, K', 4), or (k, K', 4) with `env_ids` — is sliced or picked by rows."""
+    import numpy as np
+    from . import per_env as P
+    ranges = [(int(lo), int(hi)) for lo, hi in ranges]
+    B = ranges[-1][1]
+    P.check_selectors(B, env_mask, env_ids, "set_edits")
+    ids = None if env_ids is None else P.host_ids(env_ids, B, "set_edits", any_number=True)
+    edits = edits if hasattr(edits, "shape") else np.asarray(edits)
+    per_env = len(edits.shape) == 3
+    if per_env and edits.shape[0] not in ((B,) if ids is None else (B, len(ids))):
+        raise ValueError("set_edits(edits=): one list per selected env, (%d, K', 4); got %s"
+                         % (B if ids is None else len(ids), tuple(edits.shape)))
+    out = []
+    for lo, hi in ranges:
+        kw = {}
+        if env_mask is not None:
+            kw["env_mask"] = env_mask[lo:hi]
+        sel = None
+        if ids is not None:
+            sel = np.nonzero((ids >= lo) & (ids < hi))[0]
+            if not sel.size:
+                out.append(None)
+                continue
+            kw["env_ids"] = ids[sel] - lo
+        if not per_env:
+            kw["edits"] = edits
+        elif ids is not None and edits.shape[0] == len(ids):
+            kw["edits"] = edits[sel] if isinstance(edits, np.ndarray) else edits[sel.tolist()]
+        elif ids is not None:
+            rows = ids[sel]
+            kw["edits"] = edits[rows] if isinstance(edits, np.ndarray) else edits[rows.tolist()]
+        else:
+            kw["edits"] = edits[lo:hi]
+        out.append(kw)
+    return out
+
+
 def max_over_ranks(value, device=None):
     """MAX-reduce a python float over the default process group (returns it unchanged when
     torch.distributed is not initialised)."""
@@ -226,6 +266,26 @@ class _Shards(object):
         by `ranges` (`split_params`); every shard's part is written on its own stream"""
         parts = split_params(self.ranges, env_mask=env_mask, env_ids=env_ids, **values)
         self._each(lambda k, env: None if parts[k] is None else env.set_params(**parts[k]))
+
+    def level_bank(self, seeds_or_capacity, full=False):
+        """`MultiGridEnv.level_bank` of shard 0 (every shard declares the same parameters and `level_edits`): the bank that
+        `set_levels(bank, ids)` takes; the shards read replicas of it on their own devices"""
+        return self.envs[0].level_bank(seeds_or_capacity, full=full)
+
+    def set_edits(self, edits, env_mask=None, env_ids=None):
+        """`MultiGridEnv.set_edits` for the whole batch (envs built with `level_edits=K`): the lists, `env_mask` and `env_ids`
+        in GLOBAL env order, split by `ranges` (`split_edits`); every shard's part is written on its own stream"""
+        parts = split_edits(self.ranges, edits, env_mask=env_mask, env_ids=env_ids)
+        self._each(lambda k, env: None if parts[k] is None else env.set_edits(**parts[k]))
+
+    @property
+    def edits_t(self):
+        """per shard: its env's `edits_t`"""
+        return [env.edits_t for env in self.envs]
+
+    def edit_key(self, obj):
+        """`MultiGridEnv.edit_key` in every shard (the shards register kinds in one order: one id)"""
+        return self._each(lambda k, env: env.edit_key(obj))[0]
 
     def set_levels(self, bank=None, ids=None, seeds=None, env_mask=None, env_ids=None):
         """`MultiGridEnv.set_levels` for the whole batch: `ids` / `seeds`, `env_mask` and `env_ids` in GLOBAL env order, split by

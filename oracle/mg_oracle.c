@@ -115,6 +115,8 @@ struct MgoEnv {
     int draw_words[MGO_MAX_DRAWS];                     /* RNG words each consumed; -1: not drawn */
     int param[MGO_MAX_PARAMS];                         /* the env's `_gen_grid` parameters (PARAM) */
     int8_t cond[MGO_MAX_GEN];                          /* the IFs of the last `_gen_grid`: 1 / 0, -1 not evaluated */
+    int32_t* level;                                    /* self.level: [(x, y, obj), ...] that `_gen_grid` ends with (mgo_set_edits) */
+    int32_t n_level;
     uint32_t mt[MT_N];
     int32_t mt_pos;
 };
@@ -324,6 +326,7 @@ void mgo_destroy(MgoEnv* e) {
     free(e->cell);
     free(e->cell_agents);
     free(e->cell_nagents);
+    free(e->level);
     free(e);
 }
 
@@ -528,6 +531,15 @@ static int gen_grid(MgoEnv* e, int which) {
             break;
         }
         }
+    }
+    /* `for x, y, o in self.level: self.grid.set(x, y, o)` — the last lines of a `_gen_grid` that carries a per-env list: in list
+     * order, whatever the cell holds is replaced (a later entry for a cell replaces an earlier one's), grid.set's assertion
+     * (base.py:149-152) for a cell outside the grid; the agents are placed after `_gen_grid` returns (base.py:409-412) */
+    for (int i = 0; i < e->n_level; i++) {
+        const int32_t* en = e->level + 3 * i;
+        if (en[2] < 0 || en[2] >= cfg->n_obj) return MGO_ERR_VALUE;
+        int rc = mgo_put_obj(e, en[2], en[0], en[1]);
+        if (rc != MGO_OK) return rc;
     }
     return MGO_OK;
 }
@@ -1014,6 +1026,20 @@ void mgo_get_draws(const MgoEnv* e, int32_t* draws, int32_t* words) {
 }
 
 void mgo_get_conds(const MgoEnv* e, int8_t* conds) { memcpy(conds, e->cond, sizeof(e->cond)); }
+/* env.level = [(x, y, obj), ...]: a plain list, kept until another is given; the env's next `_gen_grid` reads it */
+int32_t mgo_set_edits(MgoEnv* e, const int32_t* xyo, int32_t n) {
+    if (n < 0) return MGO_ERR_VALUE;
+    int32_t* lst = n ? (int32_t*)malloc((size_t)n * 3 * sizeof(int32_t)) : 0;
+    if (n) memcpy(lst, xyo, (size_t)n * 3 * sizeof(int32_t));
+    free(e->level);
+    e->level = lst;
+    e->n_level = n;
+    return MGO_OK;
+}
+int32_t mgo_get_edits(const MgoEnv* e, int32_t* xyo, int32_t cap) {
+    for (int i = 0; i < e->n_level && i < cap; i++) memcpy(xyo + 3 * i, e->level + 3 * i, 3 * sizeof(int32_t));
+    return e->n_level;
+}
 void mgo_set_param(MgoEnv* e, int32_t param, int32_t value) { if (param >= 0 && param < MGO_MAX_PARAMS) e->param[param] = value; }
 int32_t mgo_get_param(const MgoEnv* e, int32_t param) { return (param >= 0 && param < MGO_MAX_PARAMS) ? e->param[param] : 0; }
 

@@ -179,6 +179,14 @@ void mgo_get_conds(const MgoEnv* e, int8_t* conds);
 /* a per-env parameter of `_gen_grid` (PARAM reads it when the env next resets) */
 void mgo_set_param(MgoEnv* e, int32_t param, int32_t value);
 int32_t mgo_get_param(const MgoEnv* e, int32_t param);
+/* a per-env list of cell edits, `self.level` of a scenario whose `_gen_grid` ends with
+ *     for x, y, o in self.level: self.grid.set(x, y, o)
+ * n entries (x, y, obj), obj 0 = None, in order, copied.  Every later reset applies it after the `_gen_grid` program and before
+ * the agents are placed; a new list waits for the next reset; n = 0 is an empty list.  An entry outside the grid is grid.set's
+ * AssertionError (MGO_ERR_ASSERT) when the reset reaches it, an object id that is not in the table MGO_ERR_VALUE. */
+int32_t mgo_set_edits(MgoEnv* e, const int32_t* xyo, int32_t n);
+/* the list as held: up to `cap` entries into xyo, -> its length */
+int32_t mgo_get_edits(const MgoEnv* e, int32_t* xyo, int32_t cap);
 void mgo_set_agent_dir(MgoEnv* e, int32_t k, int32_t dir);
 void mgo_set_carrying(MgoEnv* e, int32_t k, int32_t obj);
 /* test helper: overwrite a cell with a non-agent object id (env.put_obj, base.py:655-662) */

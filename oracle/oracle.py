@@ -139,6 +139,8 @@ def lib():
         L.mgo_set_param.restype = None
         L.mgo_set_param.argtypes = [vp, C.c_int32, C.c_int32]
         L.mgo_get_param.argtypes = [vp, C.c_int32]
+        L.mgo_set_edits.argtypes = [vp, i32p, C.c_int32]
+        L.mgo_get_edits.argtypes = [vp, i32p, C.c_int32]
         L.mgo_get_prestige.argtypes = [vp, f64p]
         L.mgo_rich_obs.restype = None
         L.mgo_rich_obs.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), f64p, C.POINTER(C.c_int32)]
@@ -561,6 +563,19 @@ class OracleEnv(object):
 
     def param(self, column):
         return int(self.L.mgo_get_param(self.h, self._param_index(column)))
+
+    def set_edits(self, entries):
+        """the env's list of cell edits, ordered (x, y, obj_id) with obj_id 0 = None — what a `_gen_grid` ending in
+        `for x, y, o in self.level: self.grid.set(x, y, o)` reads: every later reset applies it after the program and before
+        the agents are placed (a running episode is untouched; [] is legal; the list stays until another is given)"""
+        a = np.ascontiguousarray(np.asarray(list(entries), np.int32).reshape(-1, 3))
+        _raise(self.L.mgo_set_edits(self.h, _p(a, C.c_int32), len(a)))
+
+    def edits(self):
+        n = self.L.mgo_get_edits(self.h, None, 0)
+        a = np.zeros((n, 3), np.int32)
+        self.L.mgo_get_edits(self.h, _p(a, C.c_int32), n)
+        return [tuple(int(v) for v in row) for row in a]
 
     def set_dir(self, k, d):
         self.L.mgo_set_agent_dir(self.h, k, d)

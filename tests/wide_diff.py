@@ -223,6 +223,13 @@ class HipSubject(object):
     def check_errors(self):
         self.env.check_errors()
 
+    def level_state(self):
+        """what a level leaves in the env besides its generator (run(ref=...) with a reference that plays levels)"""
+        e = self.env
+        return dict(episode_level=e.episode_level.cpu().numpy(),
+                    params=None if e.params_t is None else {k: v.cpu().numpy() for k, v in e.params.items()},
+                    edits=None if e.edits_t is None else e.edits_t.cpu().numpy())
+
 
 class HostEmuSubject(object):
     """tests/native/hostemu.py: the step bodies built for the host — numpy arrays, no observations"""
@@ -297,7 +304,7 @@ class _EpisodeRef(object):
 
 # ---- the driver ---------------------------------------------------------------------------------------------------------
 def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mode="same_step", episode_info=False,
-        obs_format="image", stagger=False, after_step=None, spec=None, watch=None, between=None):
+        obs_format="image", stagger=False, after_step=None, spec=None, watch=None, between=None, ref=None):
     """Step `subject` and the oracle of `spec` (default: scenarios.registered(name)) for T steps (actions
     RandomState(action_seed).randint(0, 7)).
     watch(t, envs, mask): called with the ORACLE's envs after every reset on its side — t = 0: reset() (mask: everyone);
@@ -305,15 +312,21 @@ def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mo
     ended in the call before); after a staggered reset by hand.  What a test requires of its own coverage it reads there.
     between(t, subject, envs): called with the subject and the ORACLE's envs before the first reset (t = 0) and after step t and
     all of its checks — where a run calls `set_params` on both sides: a value takes effect at an env's next reset on either.
+    A `between` that resets envs by hand on both sides returns True: the deep check then runs once more, on what the resets left.
     mode: the subject's auto-reset mode; stagger: during the first 100 steps env b is reset by hand after step b % 100 (0-based),
     subject and oracle; after_step(t, subject): called between two steps (fault injection in the driver's own tests).
+    ref: the oracle side, in place of the driver's own — an object with `envs` (the list of OracleEnvs, looked at again at every
+    check: it may swap them), reset(), reset_envs(mask), step(actions, pixels) -> (pixels or None, rewards, done, info or None),
+    and optionally extra(subject) -> [(field, differing envs, detail)], asked after every step and reset (tests/level_ref.py:
+    WideRef, whole levels).  An info field "level" is compared exactly where the reference returns one.
     -> dict(episodes (B,), draws (B,) RNG words drawn per env, blocks = draws / 624, partial_done_steps: steps on which some
     but not all envs ended, terminal_obs (B,): terminal observations compared per env, seconds: where the time went)"""
     B, n = subject.B, subject.n
     if spec is None:
         spec = scenarios.registered(name)
     use_ep = episode_info or mode == "next_step"
-    ref = _EpisodeRef(spec, seeds, mode) if use_ep else _SameStepRef(spec, seeds)
+    if ref is None:
+        ref = _EpisodeRef(spec, seeds, mode) if use_ep else _SameStepRef(spec, seeds)
     envs = ref.envs
     kind = "views" if obs_format == "encoded" else "obs"
     since = np.full(B, -1, np.int64)            # steps since the env's last in-launch reset (-1: none yet)
@@ -403,6 +416,11 @@ def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mo
                  "env %d: entry %d is %#010x, the stream's next output there is %#010x" % (b, j, head[b, j], onext[b, j]))
         lap("deep")
 
+    def check_extra(t):
+        if hasattr(ref, "extra"):
+            for field, bad, detail in ref.extra(subject):
+                fail(t, field, bad, detail)
+
     # -- the constructor's reset has run on both sides; one reset() more, as every caller of the env does
     if between is not None:
         between(0, subject, envs)
@@ -414,6 +432,7 @@ def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mo
     prev_done = np.zeros(B, bool)
     if subject.has_obs:
         check_obs(0, obs, None, what="observations of reset()")
+    check_extra(0)
     rng = np.random.RandomState(action_seed)
     partial = 0
     clock[0] = time.time()
@@ -448,6 +467,12 @@ def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mo
             bad = ~(np.abs(info["episode_return"] - want_info["episode_return"]) <= tol).all(axis=1)
             if bad.any():
                 fail(t, "info['episode_return']", np.nonzero(bad)[0])
+            if "level" in want_info:
+                bad = np.asarray(info["level"]).astype(np.int64) != want_info["level"]
+                if bad.any():
+                    b = int(np.nonzero(bad)[0][0])
+                    fail(t, "info['level']", np.nonzero(bad)[0], "env %d: got %d, want %d" % (b, info["level"][b], want_info["level"][b]))
+        check_extra(t)
         lap("compare")
         if subject.has_obs:
             if look:
@@ -478,11 +503,14 @@ def run(subject, name, seeds, T, obs_every=50, deep_every=500, action_seed=5, mo
             last_pos = count_draws(last_pos)
             if subject.has_obs and mask.any():
                 check_obs(t, obs, None, ids=np.nonzero(mask)[0], what="observations of reset(env_mask)")
+            check_extra(t)
         if after_step is not None:
             after_step(t, subject)
             clock[0] = time.time()
         if between is not None:
-            between(t, subject, envs)
+            if between(t, subject, envs) is True:       # (it reset envs by hand, on both sides: their state and RNG now)
+                last_pos = subject.mt_pos().astype(np.int64)
+                deep(t)
             clock[0] = time.time()
     subject.check_errors()
     return dict(episodes=episodes, draws=draws, blocks=draws / float(MT_N), partial_done_steps=partial,

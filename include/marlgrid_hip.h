@@ -27,6 +27,8 @@
  *                   return from the step's own launch (base.py:512, 576-581, 627-649)
  *   mg_step_render_delta / mg_step_render_delta_ex   mg_step_render (_ex: with the encode and / or an MgEpisode) that does not
  *                   store again the observation bands its output buffer already holds
+ *   mg_goal_distance  (no reference counterpart: the exact number of left / right / forward actions from every agent, or every
+ *                   state, to the step that enters a goal cell; -1 where there is no path)
  *   mg_put_obj      MultiGridEnv.put_obj (base.py:655-662)
  *   mg_place        MultiGridEnv.place_obj / try_place_obj outside _gen_grid (base.py:664-708)
  *   mg_render_frame MultiGridEnv.render's whole-grid image: MultiGrid.render(top_agent=None) +
@@ -340,6 +342,34 @@ int32_t mg_level_apply_rows(const MgConfig* cfg, const MgState* st, int32_t rule
                             const uint32_t* bank_head, const int64_t* bank_seed, int64_t* episode_level, int64_t* out_level,
                             const uint8_t* bank_params, const uint8_t* bank_edits, int32_t K, uint8_t* env_params,
                             uint8_t* env_edits, void* stream);
+
+/* Goal distance (no reference counterpart: a static analysis of the level a learner cannot get from a rollout).  For every
+ * selected env — env_mask: device uint8 [B] or NULL (= all), as mg_reset takes it — and the env's grid as it is now:
+ * agent_dist[b][k] (device int32 [B][n_agents]) = the smallest number of actions `left`, `right`, `forward` (base.py:530-585)
+ * after which agent k's `forward` ENTERS a goal cell, other agents ignored, nothing toggled, picked up or dropped; -1: no such
+ * sequence, or the agent is in no cell (not active — not yet spawned, done —, or MG_AF_EVICTED).  field (device int32
+ * [B][W][H][4] or NULL): the same number for every state, field[b][x][y][dir]; -1 where there is none and on cells an agent
+ * cannot stand on.  Rows of unselected envs are not written.
+ *   goal cell: an object with reward_kind == 1 and MG_OF_ENDS_EPISODE.  Free cell: id 0, or MG_OF_CAN_OVERLAP without
+ *   MG_OF_ENDS_EPISODE (floor, bonus tiles, open doors).  Everything else blocks — walls, keys, balls, boxes, closed and locked
+ *   doors, lava —, and so does the outside of the grid: nothing wraps, a missing border wall included.  Entering a goal ends the
+ *   agent's episode, so goal cells are never passed through; an agent that STANDS on a goal has not entered it, may turn there
+ *   and leave, and must enter a goal cell from outside.
+ * One launch, one wave per selected env, a reverse breadth-first search by levels over bit planes: in registers where
+ * 4 W <= 64 and H <= 64, in LDS otherwise (14 * 8 * W * ceil(H / 64) + 128 bytes per env: 111.7 KiB at 255 x 255); at most
+ * 4 W H + 1 levels; without `field` an env stops once its agents are all labelled.  With ghost_mode off other agents can block
+ * a path: the number is then a lower bound.
+ * Only B, W, H, n_agents, cells_stride, n_obj and obj of cfg are read (1 <= W, H <= 255), and grid and agents of st.
+ * MG_E_ARG: a NULL cfg, st, agent_dist, grid, agents or obj, or a size outside those bounds; MG_E_UNSUPPORTED: the planes do
+ * not fit LDS (no W, H <= 255 gets there). */
+int32_t mg_goal_distance(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, int32_t* agent_dist, int32_t* field,
+                         void* stream);
+/* ... with the kernel named: path 0 as above, 1 the register-resident kernel (MG_E_UNSUPPORTED unless 4 W <= 64 and H <= 64),
+ * 2 the LDS kernel; MG_E_ARG for any other path.  NOT for hosts: it exists so that the project's own tests and measurements can
+ * hold the two kernels to each other, it may change or go with either kernel, and no binding outside this repository should
+ * depend on it — mg_goal_distance is the call. */
+int32_t mg_goal_distance_path(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, int32_t* agent_dist,
+                              int32_t* field, int32_t path, void* stream);
 
 /* actions: device [B][n_agents], element size `action_bytes` in {1,4,8} (little-endian ints).
  * rewards: device float32 [B][n_agents].  Sets st->done[b].

@@ -108,6 +108,7 @@ class PlaceStats(C.Structure):
 
 
 LEVEL_PUBLISH, LEVEL_PENDING, LEVEL_MASK = 0, 1, 2      # MG_LEVEL_* (mg_level_apply's rule)
+GOAL_PATH_AUTO, GOAL_PATH_REG, GOAL_PATH_LDS = 0, 1, 2  # mg_goal_distance_path's path
 
 DELTA_FORCE = 1            # MG_DELTA_FORCE (mg_step_render_delta)
 
@@ -144,7 +145,8 @@ SYMBOLS = ["mg_abi_version", "mg_struct_sizes", "mg_host_flag_alloc", "mg_host_f
            "mg_step_render_delta", "mg_step_render_delta_ex",
            "mg_spec_info_struct_size", "mg_render_specialize", "mg_step_render_spec", "mg_render_obs_spec",
            "mg_render_spec_release", "mg_rtc_source",
-           "mg_level_seed", "mg_level_apply", "mg_level_apply_rows"]
+           "mg_level_seed", "mg_level_apply", "mg_level_apply_rows",
+           "mg_goal_distance", "mg_goal_distance_path"]
 
 _lib = None
 _path = LIB_PATH
@@ -215,6 +217,9 @@ def lib():
     L.mg_level_apply.argtypes = [C.POINTER(Config), C.POINTER(State), i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     # (... out_level, bank_params, bank_edits, K, env_params, env_edits, stream)
     L.mg_level_apply_rows.argtypes = [C.POINTER(Config), C.POINTER(State), i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    # (cfg, st, env_mask, agent_dist, field, stream) / (..., field, path, stream)
+    L.mg_goal_distance.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp, vp, vp]
+    L.mg_goal_distance_path.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp, vp, i32, vp]
     L.mg_reset.argtypes = [C.POINTER(Config), C.POINTER(State), C.POINTER(GenProgram), vp, vp]
     L.mg_step.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp]
     L.mg_step_render.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp]

@@ -37,6 +37,7 @@ from . import per_env, rendering, seeding, spaces
 from .agents import GridAgentInterface
 from .gen_edits import EditTable
 from .gen_params import ParamTable
+from .goal import EnvGoal
 from .gen_recorder import GenDraw, GenRecorder, _NO_BRANCH, _any_draw, _gen_add, _trace, decode_program, pack_program
 from .levels import EnvLevels, LevelBank
 from .objects import COLOR_TO_IDX, OBJECT_TYPES, BonusTile, Box, Door, Goal, Key, Wall, WorldObj
@@ -566,6 +567,7 @@ class MultiGridEnv(object):
         self._prog_cache = {}
         self._params = ParamTable(self)     # the per-env parameters of `_gen_grid` (gen_params.py)
         self._levels = EnvLevels(self)      # replayable levels (levels.py): nothing is allocated or launched until set_levels
+        self._goal = EnvGoal(self)          # goal distance (goal.py): nothing is allocated or launched until goal_distance
         # level_edits=K (0..64): every env holds a list of K cell edits (x, y, kind, on) that its every reset applies behind
         # what `_gen_grid` laid out and before the agents are placed (an EDITS op at the end of the reset program; set_edits).
         # 0: no table, no op — recordings, programs and launches are what they were
@@ -1080,6 +1082,36 @@ class MultiGridEnv(object):
     _level_bank = property(lambda self: self._levels.bank)
     _own_bank = property(lambda self: self._levels.own_bank)
     _level_of_env = property(lambda self: self._levels.level_of_env)
+
+    # ---- goal distance: what an optimal agent would need, per env, from the env's own grid -----------------------------------
+    @_on_device
+    def goal_distance(self, env_mask=None, env_ids=None, field=False, _path=None):
+        """The exact number of actions `left` / `right` / `forward` after which each agent's `forward` ENTERS a goal cell, on its
+        env's grid as it is now: the env-owned (B, n) int32 tensor, -1 where no such sequence exists or the agent is in no cell
+        (not yet spawned, done, evicted by put_obj).  With `field=True` the pair (dist, field): field (B, W, H, 4) int32 holds
+        the same number for every state, field[b, x, y, dir], -1 where there is none and on cells no agent can stand on.  Both
+        are updated for the selected envs only — all, those of `env_mask` ((B,) bool; step()'s `info["reset"]` as it is) or
+        those listed in `env_ids` (host ids are checked, ValueError; a device tensor's ids outside the batch select nothing) — and
+        start at -1; they are made at the first call.
+
+        The analysis is static: other agents are ignored, nothing is toggled, picked up or dropped.  Free cells are empty ones
+        and objects that can be overlapped without ending the episode (floor, bonus tiles, open doors); walls, keys, balls,
+        boxes, closed and locked doors and lava block, and so does the outside of the grid (a border wall removed by an edit
+        included).  Entering a goal ends the agent's episode, so goals are never passed through, and an agent standing on a
+        goal has to leave and come back.  With `ghost_mode=False` other agents can stand in the way: the number is then a
+        lower bound.
+
+        One launch on the current stream (mg_goal_distance: a wave per selected env), nothing is read back, no host
+        synchronisation; an env that never calls it allocates and launches nothing.  Derived values: no part of state_dict()."""
+        return self._goal.distance(env_mask, env_ids, field, _path)
+
+    @_on_device
+    def optimal_return(self, dist=None):
+        """(B, n) float64: what an agent that takes a shortest path from here earns — R * (1 - 0.9 * (step_count + d) /
+        max_steps), R without reward_decay, and 0 where d < 0 (no path) or step_count + d > max_steps (the episode is truncated
+        first).  `dist`: a (B, n) tensor of distances, default `goal_distance()` of every env now.  R is the reward the
+        registered Goal kinds share (ValueError if they differ or there is none).  Torch ops only."""
+        return self._goal.optimal_return(dist)
 
     # ---- branching on a draw: one recorded run of `_gen_grid` per path, merged into one guarded program --------------
     def _fork(self, d):

@@ -190,6 +190,23 @@ int32_t mg_level_apply_rows(const MgConfig* cfg, const MgState* st, int32_t rule
                                           (hipStream_t)stream));
 }
 
+int32_t mg_goal_distance_path(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, int32_t* agent_dist, int32_t* field,
+                              int32_t path, void* stream) {
+    if (!cfg || !st || !agent_dist || !st->grid || !st->agents || !cfg->obj) return MG_E_ARG;
+    if (cfg->B < 0 || cfg->W < 1 || cfg->H < 1 || cfg->W > 255 || cfg->H > 255 || cfg->n_agents < 1 || cfg->n_agents > MG_MAX_AGENTS)
+        return MG_E_ARG;
+    if (cfg->cells_stride < cfg->W * cfg->H || cfg->n_obj < 1 || cfg->n_obj > MG_MAX_OBJ) return MG_E_ARG;
+    if (path < 0 || path > 2) return MG_E_ARG;
+    int unsupported = 0;
+    const hipError_t e = mg::launch_goal_distance(*cfg, *st, env_mask, agent_dist, field, path, (hipStream_t)stream, &unsupported);
+    return unsupported ? MG_E_UNSUPPORTED : rc(e);
+}
+
+int32_t mg_goal_distance(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, int32_t* agent_dist, int32_t* field,
+                         void* stream) {
+    return mg_goal_distance_path(cfg, st, env_mask, agent_dist, field, 0, stream);
+}
+
 int32_t mg_episode_struct_size(void) { return (int32_t)sizeof(MgEpisode); }
 
 int32_t mg_step_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,

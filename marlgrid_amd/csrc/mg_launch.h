@@ -44,4 +44,8 @@ hipError_t launch_level_apply_rows(const MgConfig& cfg, const MgState& st, int r
                                    int n_slots, const uint32_t* bank_mt, const int32_t* bank_pos, const uint32_t* bank_head,
                                    const int64_t* bank_seed, int64_t* episode_level, int64_t* out_level, const uint8_t* bank_params,
                                    const uint8_t* bank_edits, int K, uint8_t* env_params, uint8_t* env_edits, hipStream_t s);
+// goal distance (mg_goal_dist.hip): path 0 — the register-resident kernel where the grid fits a wave, else the LDS one —, 1 / 2
+// force either; *unsupported = 1 and nothing launched when the forced or the only path cannot take the shape
+hipError_t launch_goal_distance(const MgConfig& cfg, const MgState& st, const uint8_t* mask, int32_t* agent_dist, int32_t* field,
+                                int path, hipStream_t s, int* unsupported);
 }  // namespace mg

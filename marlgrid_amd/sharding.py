@@ -310,6 +310,15 @@ class _Shards(object):
         """per shard: its env's `episode_level`"""
         return [env.episode_level for env in self.envs]
 
+    def goal_distance(self, env_mask=None, env_ids=None, field=False):
+        """`MultiGridEnv.goal_distance` for the whole batch: `env_mask` / `env_ids` in GLOBAL env order, split by `ranges`; every
+        shard launches on its own stream.  Per shard: its env's (rows, n) tensor, or with `field=True` its (dist, field) pair
+        (a shard none of `env_ids` falls into selects nothing and returns its tensors as they are)."""
+        import numpy as np
+        parts = split_params(self.ranges, env_mask=env_mask, env_ids=env_ids, _who="goal_distance")
+        none = {"env_ids": np.zeros(0, np.int64)}
+        return self._each(lambda k, env: env.goal_distance(field=field, **(none if parts[k] is None else parts[k])))
+
     @property
     def params(self):
         """per shard: its env's `params` (name -> the shard's (rows,) uint8 column)"""

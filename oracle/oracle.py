@@ -475,9 +475,10 @@ class OracleEnv(object):
         except Exception:
             pass
 
-    def reset(self):
+    def reset(self, observe=True):
+        """observe=False: the reset alone, no observations rendered (-> None)"""
         _raise(self.L.mgo_reset(self.h, 1))
-        return self.gen_obs()
+        return self.gen_obs() if observe else None
 
     def step(self, actions, return_order=False):
         assert len(actions) == self.n                     # base.py:508

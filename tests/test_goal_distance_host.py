@@ -186,3 +186,100 @@ def test_other_grids():
 def test_scratch_fits_lds_at_the_largest_grid():
     import hostemu_goal as HG
     assert HG.lib().gd_scratch_bytes(255, 255) == 14 * 8 * 255 * 4 + 128 <= 160 * 1024
+
+
+# ---- the edge shapes of both kernels (tests/goal_cases.py; the device runs the same in tests/test_hip_goal_distance.py) ------
+def _edge_shapes():
+    import goal_cases
+    return goal_cases.REG_SHAPES + goal_cases.LDS_SHAPES
+
+
+@pytest.mark.parametrize("W,H", _edge_shapes())
+def test_edge_shapes(W, H):
+    """lane 63 owning a plane, bit 63, W != H, one column, one row, more agents than plane lanes; H on both sides of every
+    word boundary; the two shapes around 64 KiB of scratch.  The coverage conditions are asserted on the reference's field
+    (goal_cases.edge): states with a distance in the first and last row and column and in every row beside a word boundary."""
+    import ctypes as C
+    import goal_cases
+    import hostemu_goal as HG
+    case, dist, field = goal_cases.edge(W, H)
+    fits = goal_cases.reg_fits(W, H)
+    assert fits == ((W, H) in goal_cases.REG_SHAPES)
+    assert HG.lib().gd_scratch_bytes(W, H) == goal_cases.scratch_bytes(W, H)
+    assert [p for p, _ in _paths(case.cfg)] == ["general", "general"] + ["reg"] * fits
+    _check_all(case.cfg, case.state, dist, field)
+    if not fits:        # the register kernel is not launched for the shape
+        d = np.full(dist.shape, -7, np.int32)
+        assert HG.lib().gd_reg(C.byref(case.cfg), C.byref(case.state), None, d.ctypes.data, None) == -1 and (d == -7).all()
+
+
+def test_edge_shapes_sit_where_they_are_meant_to():
+    import goal_cases
+    assert goal_cases.scratch_bytes(146, 193) == 64 * 1024 and goal_cases.scratch_bytes(147, 193) == 65984
+    assert len(_edge_shapes()) == 22 and len(set(_edge_shapes())) == 22
+    for W, H in goal_cases.REG_SHAPES:
+        n = goal_cases.edge(W, H)[0].cfg.n_agents
+        assert n == (32 if W <= 3 else 6) and (n > 4 * W) == (W <= 3)
+
+
+# ---- following the field from the middle of an episode and across truncation ---------------------------------------------------
+FOLLOW = [(14, 0), (20, 6), (100, 30)]          # (max_steps, warm-up steps); the device runs the same cases
+REW_TOL = 1e-6
+
+
+@pytest.mark.parametrize("M,warm", FOLLOW)
+def test_following_the_field_pays_what_optimal_return_says(M, warm):
+    """MarlGrid-1AgentCluttered15x15-v0, 512 envs, `warm` steps of left / right / forward, then every step the action whose
+    successor has the smaller field value.  optimal_return's formula, restated here, is held to the rewards the step body
+    pays: where d >= 0 and step_count + d <= max_steps the agent is done at exactly step d with exactly that return; everywhere
+    else the formula says 0 and nothing is earned — at step_count + d == max_steps + 1 the episode is truncated one step
+    before the goal."""
+    import hostemu
+    import hostemu_goal as HG
+    B = 512
+    emu = hostemu.HostEmu("MarlGrid-1AgentCluttered15x15-v0", B, 1337 + np.arange(B), max_steps=M)
+    emu.reset()
+    rng = np.random.RandomState(9)
+    for _ in range(warm):
+        emu.step(rng.randint(0, 3, size=(B, 1)))
+    W, H = emu.env.width, emu.env.height
+    grid = emu.grid[:, :W * H].reshape(B, W, H).copy()
+    dist, field = HG.run(emu._cfg(), emu.state, "reg")
+    goal = G.classify(grid, *G.kinds_of(emu.env))[1]
+    sc = emu.step_count.astype(np.int64).copy()
+    d0 = dist[:, 0].astype(np.int64)
+    running = ~emu.done.astype(bool)
+    assert (sc[running] == warm).all() and running.any()
+    assert (dist[~running, 0] == -1).all()      # (an env that ended in the warm-up: its agent is done, in no cell)
+    t_goal = sc + d0
+    pays = (d0 >= 0) & (t_goal <= M)
+    want = np.where(pays, 1.0 * (1.0 - 0.9 * (t_goal / float(M))), 0.0)
+    assert emu.env.reward_decay and emu.env.max_steps == M
+    if M < 100:     # the truncation rule is met on both sides
+        assert (running & (d0 >= 0) & (t_goal == M)).any() and (running & (d0 >= 0) & (t_goal == M + 1)).any()
+    assert pays.any() and (d0 < 0).any()
+    big = np.iinfo(np.int32).max
+    f = np.where(field < 0, big, field).astype(np.int64)
+    b = np.arange(B)
+    dx, dy = np.array([1, 0, -1, 0]), np.array([0, 1, 0, -1])
+    done_at = np.full(B, -1, np.int64)
+    got = np.zeros(B)
+    over = ~running
+    for t in range(1, M - warm + 1):
+        pos, d, _ = G.unpack_records(emu.rec)
+        x, y, d = pos[:, 0, 0], pos[:, 0, 1], d[:, 0]
+        fx, fy = np.clip(x + dx[d], 0, W - 1), np.clip(y + dy[d], 0, H - 1)
+        v_fwd = np.where(goal[b, fx, fy], 0, f[b, fx, fy, d])
+        vals = np.stack([f[b, x, y, (d + 3) & 3], f[b, x, y, (d + 1) & 3], v_fwd], 1)
+        here = f[b, x, y, d]
+        act = np.where(here >= big, rng.randint(0, 3, size=B), vals.argmin(1))
+        rew, done = emu.step(act[:, None])
+        got += np.where(over, 0.0, rew[:, 0].astype(np.float64))       # an env that is done pays nothing that counts
+        _, _, fl = G.unpack_records(emu.rec)
+        newly = ((fl[:, 0] & N.AF_DONE) != 0) & (done_at < 0) & ~over
+        done_at = np.where(newly, t, done_at)
+        over |= done
+    assert over.all()
+    assert np.array_equal(done_at[pays], d0[pays])
+    assert np.abs(got[pays] - want[pays]).max() <= REW_TOL
+    assert (done_at[~pays] < 0).all() and (got[~pays] == 0).all() and (want[~pays] == 0).all()

@@ -1,7 +1,12 @@
 """GPU (-m gpu): mg_goal_distance — `env.goal_distance()` / `optimal_return()` — against tests/goal_ref.py on the state read
 back from the env, the register-resident kernel and the LDS kernel forced in turn and held to each other, env selection,
 pipelines and device shards, the mazes and the hand-made grids through the bare C ABI, and an end-to-end run in which an agent
-that follows the field arrives at exactly the step the field names with exactly the return `optimal_return` names."""
+that follows the field arrives at exactly the step the field names with exactly the return `optimal_return` names.
+
+Further down: the edge shapes of both kernels (tests/goal_cases.py); what a cell is, read from what one `forward` of the step
+launch does (tests/goal_probe.py), held to the flag rule and to the field; the field followed from the middle of an episode and
+across truncation; and the running use — `goal_distance(env_mask=info["reset"])` every step under auto-reset — against a host
+mirror, with the bound that no episode returns more than `optimal_return` said at its start."""
 import ctypes as C
 import os
 import sys
@@ -184,6 +189,11 @@ def _check_raw(grid, agents):
     free, goal = G.classify(np.asarray(grid), *case.kinds())
     field = np.stack([G.field_queue(free[b], goal[b]) for b in range(free.shape[0])])
     dist = G.agents_from_field(field, *G.unpack_records(case.rec))
+    return _check_case(case, dist, field)
+
+
+def _check_case(case, dist, field, without_field=None):
+    """without_field: also run without the field (the sentinel rows untouched); by default where W * H <= 10 000"""
     dev = _Device(case)
     W, H = case.cfg.W, case.cfg.H
     fits = 4 * W <= 64 and H <= 64
@@ -191,7 +201,7 @@ def _check_raw(grid, agents):
     for path in ([N.GOAL_PATH_REG, N.GOAL_PATH_AUTO] if fits else []) + [N.GOAL_PATH_LDS]:
         d, f = dev.run(path)
         assert np.array_equal(d, dist) and np.array_equal(f, field), path
-        if W * H <= 10000:      # (the largest maze is 32 509 levels a run: once)
+        if (W * H <= 10000) if without_field is None else without_field:      # (the largest maze is 32 509 levels a run: once)
             d, f = dev.run(path, field=False)
             assert np.array_equal(d, dist) and (f == -7).all(), path
     return dist, field
@@ -369,3 +379,277 @@ def test_contract_error_codes():
     assert L.mg_goal_distance_path(C.byref(wide.cfg), C.byref(wide.state), None, wide.dist.data_ptr(), None, N.GOAL_PATH_REG, None) \
         == N.E_UNSUPPORTED
     assert L.mg_goal_distance(cfg, st, None, dist, None, None) == 0
+
+
+# ---- the edge shapes of both kernels (tests/goal_cases.py; tests/test_goal_distance_host.py runs the same on the host builds) ----
+def _edge_shapes():
+    import goal_cases
+    return goal_cases.REG_SHAPES + goal_cases.LDS_SHAPES
+
+
+@pytest.mark.parametrize("W,H", _edge_shapes())
+def test_edge_shapes(W, H):
+    """goal_reg_kernel with lane 63 owning a plane (W = 16), bit 63 (H = 64), W != H, one column, one row and 32 agents on at
+    most 12 plane lanes; goal_lds_kernel one past each of the other's limits, with H on both sides of every word boundary, and
+    around 64 KiB of dynamic LDS: 146 x 193 asks for exactly 65 536 bytes without the attribute, 147 x 193 for 65 984 with it
+    (what a process accepts there BEFORE any larger grid raised the kernel's limit: test_first_lds_launch_of_a_process_at_64_kib).
+    Each path the shape admits, with the field and without (the sentinel rows untouched) at every shape; the coverage conditions
+    are asserted on the reference's field in goal_cases.edge."""
+    import goal_cases
+    case, dist, field = goal_cases.edge(W, H)
+    fits = goal_cases.reg_fits(W, H)
+    assert fits == ((W, H) in goal_cases.REG_SHAPES)
+    _check_case(case, dist, field, without_field=True)     # (at most 377 levels a run, at 146 x 193)
+    if not fits:
+        import torch
+        dev = _Device(case)
+        rc = N.lib().mg_goal_distance_path(C.byref(dev.cfg), C.byref(dev.state), None, dev.dist.data_ptr(), dev.field.data_ptr(),
+                                           N.GOAL_PATH_REG, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        assert rc == N.E_UNSUPPORTED and bool((dev.dist == -7).all()) and bool((dev.field == -7).all())
+
+
+@pytest.mark.parametrize("W,H,attribute", [(146, 193, False), (147, 193, True)])
+def test_first_lds_launch_of_a_process_at_64_kib(W, H, attribute):
+    """hipFuncSetAttribute acts on the function for the rest of the process, and the mazes raise goal_lds_kernel's limit before
+    test_edge_shapes runs: what THIS process accepts at 65 536 bytes says nothing.  A fresh child process (tests/goal_first_launch.py)
+    whose first goal_lds_kernel launch is 146 x 193 — exactly 64 KiB of dynamic LDS, `lds > 64 * 1024` false, no attribute set —
+    must get return code 0 and the reference's numbers; and one whose first is 147 x 193, 65 984 bytes with the attribute."""
+    import subprocess
+    import goal_cases
+    assert (goal_cases.scratch_bytes(W, H) > 64 * 1024) == attribute
+    here = os.path.dirname(os.path.abspath(__file__))
+    out = subprocess.run([sys.executable, os.path.join(here, "goal_first_launch.py"), str(W), str(H)], stdout=subprocess.PIPE,
+                         stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
+    assert out.returncode == 0, out.stdout[-2000:]
+    assert "FIRST_LDS_LAUNCH_OK %d %d %d" % (W, H, goal_cases.scratch_bytes(W, H)) in out.stdout, out.stdout[-2000:]
+
+
+# ---- what a cell is, read from what `forward` does (tests/goal_probe.py; the oracle's verdicts: tests/test_oracle_goal_kinds.py) ----
+def _probe(name, prepare=None):
+    """-> (env, env 0's pre-step grid, the agents' cells after reset, verdict map, counts, env 0's field per path)"""
+    import goal_probe as P
+    import product_envs
+    import scenarios
+    import torch
+    spec = scenarios.registered(name)
+    plan = P.Plan(spec["W"], spec["H"])
+    B = plan.B
+    env = product_envs.build(name, batch_size=B, seeds=[P.SEED] * B, place_obs=False, auto_reset=False, strict=False)
+    env.reset()
+    if prepare is not None:
+        prepare(env)
+    grid = env.grid.grid.cpu().numpy()
+    rec = env.agent_state.cpu().numpy()
+    pos0, _, flags = G.unpack_records(rec)
+    P.assert_probe_ready(grid, flags)
+    fields = {}
+    for path in (["reg"] if 4 * plan.W <= 64 and plan.H <= 64 else []) + ["lds", None]:
+        env.goal_distance(field=True)
+        env._goal.field.fill_(-7)
+        fields[path] = env.goal_distance(env_ids=[0], field=True, _path=path)[1].cpu().numpy()
+        assert (fields[path][1:] == -7).all()
+        fields[path] = fields[path][0]
+    env.agent_state[:, 0] = torch.from_numpy(plan.records(rec[:, 0]).view(np.int64)).to(env.device)
+    _, rew, _, _ = env.step(torch.from_numpy(plan.actions(env.num_agents)).to(env.device))
+    env.check_errors()
+    assert int(env.error_t.abs().sum()) == 0
+    pos, _, fl = G.unpack_records(env.agent_state.cpu().numpy())
+    assert np.array_equal(pos[~plan.probed, 0], pos0[~plan.probed, 0])
+    verdict, counts = plan.verdicts(pos[:, 0], (fl[:, 0] & N.AF_DONE) != 0, rew[:, 0].cpu().numpy())
+    return env, grid[0], pos0[0], verdict, counts, fields
+
+
+def _hold_probe(env, grid, verdict, fields, leave_out=()):
+    import goal_probe as P
+    return P.hold(*G.classify(grid, *G.kinds_of(env)), verdict, fields, leave_out)
+
+
+def _probe_scenes():
+    import goal_probe as P
+    return P.SCENES
+
+
+@pytest.mark.parametrize("name", _probe_scenes())
+def test_probed_cells_are_the_rule_and_give_the_field(name):
+    """every state of one grid probed with one `forward` of the step launch, in 4 W H envs: the verdicts equal the flag rule cell
+    for cell, and the reverse queue search over the PROBED maps equals the field of both kernels for that grid"""
+    import goal_probe as P
+    env, grid, pos0, verdict, counts, fields = _probe(name)
+    if name == "Limit-3Agent100Kinds24x24":
+        assert len(np.unique(grid)) == 102 and sorted(fields, key=str) == [None, "lds"]
+        assert counts == (1800, 64, 232), counts        # (what the host build of the step bodies gives)
+    if name == P.NOGHOST:       # other agents block: exactly the two cells under agents 1 and 2 read differently
+        others = [(int(x), int(y)) for x, y in pos0[1:]]
+        assert len(set(others)) == 2 and not env.ghost_mode
+        want = _hold_probe(env, grid, verdict, fields, leave_out=others)
+    else:
+        assert env.ghost_mode
+        want = _hold_probe(env, grid, verdict, fields)
+    if name == "Edge-HumanPlayerConfig":        # bonus tiles, no goal
+        assert (verdict != P.GOAL).all() and (want == -1).all()
+    else:
+        assert (want > 0).any() and (want == -1).any()
+
+
+def test_zoo_of_kinds():
+    """a 9 x 7 room, one object of every kind put after the constructor — goal_distance right after the registry and the object
+    table grew —: the step's verdict per kind is the table of MultiGridEnv.goal_distance's docstring — free: open Door, Floor,
+    BonusTile; goal: Goal; everything else blocks"""
+    import goal_probe as P
+    from marlgrid_amd import objects as PO
+    zoo = P.zoo_objects(PO)
+    placed = {}
+
+    def prepare(env):
+        pos = env.agent_pos.cpu().numpy()
+        assert (pos == pos[0]).all()
+        n_before = len(env.obj_reg.objs)
+        for (kind, obj), (x, y) in zip(zoo, P.zoo_cells(env.width, env.height, pos[0])):
+            env.put_obj(obj, x, y)
+            placed[kind] = (x, y)
+        assert len(env.obj_reg.objs) > n_before
+
+    env, grid, _, verdict, _, fields = _probe(P.ZOO, prepare)
+    assert sorted(fields, key=str) == [None, "lds", "reg"] and env.batch_size == 252
+    assert len({int(grid[c]) for c in placed.values()}) == len(zoo)
+    assert [verdict[placed[kind]] for kind, _ in zoo] == P.ZOO_VERDICTS
+    want = _hold_probe(env, grid, verdict, fields)
+    assert (want > 0).any()
+
+
+# ---- following the field from the middle of an episode and across truncation ---------------------------------------------------
+@pytest.mark.parametrize("M,warm", [(14, 0), (20, 6), (100, 30)])
+def test_following_the_field_pays_what_optimal_return_says(M, warm):
+    """MarlGrid-1AgentCluttered15x15-v0, 512 envs, `warm` steps of left / right / forward (numpy's RandomState(9), as
+    tests/test_goal_distance_host.py draws them), then the field is followed.  Where d >= 0 and step_count + d <= max_steps the
+    agent is done at exactly step d and its return is optimal_return's within REW_TOL; everywhere else optimal_return is 0 and
+    nothing is earned — at step_count + d == max_steps + 1 the episode is truncated one step before the goal.  Rewards count
+    until the env is done."""
+    import torch
+    from marlgrid_amd.envs import make
+    B = 512
+    env = make("MarlGrid-1AgentCluttered15x15-v0", batch_size=B, seeds=1337 + np.arange(B), max_steps=M, auto_reset=False,
+               place_obs=False)
+    env.reset()
+    dev, W, H = env.device, env.width, env.height
+    rng = np.random.RandomState(9)
+    over = torch.zeros(B, dtype=torch.bool, device=dev)
+    for _ in range(warm):
+        over = env.step(torch.from_numpy(rng.randint(0, 3, size=(B, 1))).to(dev))[2].clone()
+    dist, field = env.goal_distance(field=True)
+    d0 = dist[:, 0].clone().long()
+    want = env.optimal_return(dist)[:, 0].clone()
+    sc = env.step_count.clone().long()
+    assert env.max_steps == M and env.reward_decay and bool((sc[~over] == warm).all()) and bool((d0[over] < 0).all())
+    t_goal = sc + d0
+    pays = (d0 >= 0) & (t_goal <= M)
+    assert bool(pays.any()) and bool((d0 < 0).any())
+    if M < 100:     # the truncation rule is met on both sides
+        assert bool(((d0 >= 0) & (t_goal == M)).any()) and bool(((d0 >= 0) & (t_goal == M + 1)).any())
+    else:
+        assert warm == 30 and bool((sc[~over] == 30).all())
+    assert torch.equal(want == 0, ~pays) and bool((want[pays] > 0).all())
+    big = torch.iinfo(torch.int32).max
+    f = torch.where(field < 0, torch.full_like(field, big), field).long()
+    dx = torch.tensor([1, 0, -1, 0], device=dev)
+    dy = torch.tensor([0, 1, 0, -1], device=dev)
+    b = torch.arange(B, device=dev)
+    goal = torch.from_numpy(G.classify(env.grid.grid.cpu().numpy(), *G.kinds_of(env))[1]).to(dev)
+    done_at = torch.full((B,), -1, dtype=torch.long, device=dev)
+    got = torch.zeros(B, dtype=torch.float64, device=dev)
+    gen = torch.Generator(dev).manual_seed(11)
+    for t in range(1, M - warm + 1):
+        pos, d = env.agent_pos[:, 0], env.agent_dir[:, 0]
+        x, y = pos[:, 0], pos[:, 1]
+        fx, fy = (x + dx[d]).clamp(0, W - 1), (y + dy[d]).clamp(0, H - 1)
+        v_fwd = torch.where(goal[b, fx, fy], torch.zeros_like(x), f[b, fx, fy, d])
+        vals = torch.stack([f[b, x, y, (d + 3) & 3], f[b, x, y, (d + 1) & 3], v_fwd], 1)
+        here = f[b, x, y, d]
+        act = torch.where(here >= big, torch.randint(0, 3, (B,), device=dev, generator=gen), vals.argmin(1))
+        _, rew, done, _ = env.step(act.unsqueeze(1))
+        got += torch.where(over, torch.zeros_like(got), rew[:, 0].double())      # an env that is done pays nothing that counts
+        newly = env.agent_done[:, 0] & (done_at < 0) & ~over
+        done_at = torch.where(newly, torch.full_like(done_at, t), done_at)
+        over = over | done
+    env.check_errors()
+    assert bool(over.all())
+    assert torch.equal(done_at[pays], d0[pays])
+    assert float((got[pays] - want[pays]).abs().max()) <= REW_TOL
+    assert bool((done_at[~pays] < 0).all()) and bool((got[~pays] == 0).all())
+
+
+# ---- the running use: goal_distance(env_mask=info["reset"]) under auto-reset (examples/level_regret.py) ------------------------
+def _reference_rows(env, m):
+    """(dist, field) of goal_ref for the envs of the bool array `m`, from the state as it is on the device now"""
+    free, goal = G.classify(env.grid.grid.cpu().numpy()[m], *G.kinds_of(env))
+    field = G.field_levels(free, goal)
+    dist = G.agents_from_field(field, env.agent_pos.cpu().numpy()[m], env.agent_dir.cpu().numpy()[m], env.agent_flags.cpu().numpy()[m])
+    return dist, field
+
+
+@pytest.mark.parametrize("auto_reset,episode_info", [(True, False), ("next_step", True)])
+def test_masked_by_the_steps_own_reset_mask_under_auto_reset(auto_reset, episode_info):
+    """MarlGrid-3AgentCluttered15x15-v0, 259 envs (a 4-wave workgroup of the register kernel and a ragged tail), max_steps=25, 150
+    steps of left / right / forward (nothing is toggled: an episode's grid is static).  Every step
+    `goal_distance(env_mask=..., field=True)` with the mask exactly as step() returned it — info["reset"] where there is episode
+    info, `done` under same-step reset, where the step that ends an episode is the one that resets it — against a host mirror:
+    the reset envs hold the reference of their new grid, every other env still holds its episode's first analysis.  And a
+    theorem, not a measurement: in ghost mode on a static grid no policy beats a shortest path, so every completed episode's
+    return per agent is at most optimal_return taken at that episode's start (+ REW_TOL), and 0 where the start distance was
+    -1 — which a distance that is too LARGE fails.  Required of the run: steps that select no env, steps that select one, a
+    step that selects more than a workgroup's four, and at least 5 episodes started in every env."""
+    import torch
+    from marlgrid_amd.envs import make
+    B, M, steps = 259, 25, 150
+    env = make(S15, batch_size=B, seeds=1337 + np.arange(B), max_steps=M, auto_reset=auto_reset, episode_info=episode_info,
+               place_obs=False)
+    assert env.ghost_mode
+    env.reset()
+    n, dev = env.num_agents, env.device
+    # Three random walkers do not all reach the goal within 25 steps: left alone, every env is truncated at the same step and
+    # every mask is all or nothing.  Envs 1 .. 11 therefore begin their first episode at step_count 2, 4, .. 22 — they are
+    # truncated alone, 25 (26) steps apart from then on; optimal_return reads step_count itself, so the bound stands.
+    env.step_count[:12] = torch.arange(0, 24, 2, dtype=env.step_count.dtype, device=dev)
+    dist, field = env.goal_distance(field=True)
+    every = np.ones(B, bool)
+    m_dist, m_field = _reference_rows(env, every)
+    assert np.array_equal(dist.cpu().numpy(), m_dist) and np.array_equal(field.cpu().numpy(), m_field)
+    best = env.optimal_return(dist).cpu().numpy().copy()
+    start_d = m_dist.copy()
+    sc = env.step_count.cpu().numpy().astype(np.int64)[:, None]      # the staggered envs' bound: optimal_return reads step_count
+    assert sc[:12, 0].tolist() == list(range(0, 24, 2)) and (sc[12:] == 0).all()
+    formula = np.where((m_dist < 0) | (sc + m_dist > M), 0.0, 1.0 - 0.9 * (sc + m_dist) / float(M))
+    fresh = np.where(m_dist < 0, 0.0, 1.0 - 0.9 * m_dist / float(M))        # ... what the same distance is worth from step 0
+    late = np.zeros((B, n), bool)
+    late[1:12] = m_dist[1:12] > 0
+    assert np.abs(best - formula).max() <= 1e-12 and late.any() and (best[late] < fresh[late]).all()
+    ret = np.zeros((B, n))
+    starts = np.ones(B, np.int64)
+    selected, episodes, paid = [], 0, 0
+    rng = np.random.RandomState(3)
+    for t in range(steps):
+        _, rew, done, info = env.step(torch.from_numpy(rng.randint(0, 3, size=(B, n))).to(dev))
+        mask = info["reset"] if episode_info else done
+        dist, field = env.goal_distance(env_mask=mask, field=True)
+        opt = env.optimal_return(dist).cpu().numpy()
+        m, fin = mask.cpu().numpy().astype(bool), done.cpu().numpy().astype(bool)
+        ret += rew.cpu().numpy().astype(np.float64)
+        returns = info["episode_return"].cpu().numpy() if episode_info else ret
+        if episode_info:
+            assert np.abs(returns[fin] - ret[fin]).max(initial=0.0) <= REW_TOL      # (the two ways of summing agree)
+        assert (returns[fin] <= best[fin] + REW_TOL).all(), t
+        assert (returns[fin][start_d[fin] < 0] == 0).all(), t
+        episodes += int(fin.sum())
+        paid += int((returns[fin] > 0).sum())
+        ret[fin] = 0
+        if m.any():
+            m_dist[m], m_field[m] = _reference_rows(env, m)
+            best[m], start_d[m] = opt[m], m_dist[m]
+            assert (env.step_count.cpu().numpy()[m] == 0).all()
+        assert np.array_equal(dist.cpu().numpy(), m_dist) and np.array_equal(field.cpu().numpy(), m_field), t
+        selected.append(int(m.sum()))
+        starts += m
+    env.check_errors()
+    assert 0 in selected and 1 in selected and max(selected) > 4 and starts.min() >= 5
+    assert episodes >= 5 * B and paid > 0       # (some agents did reach a goal: the bound was not held by zeros alone)

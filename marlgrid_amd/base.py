@@ -40,6 +40,7 @@ from .gen_params import ParamTable
 from .goal import EnvGoal
 from .gen_recorder import GenDraw, GenRecorder, _NO_BRANCH, _any_draw, _gen_add, _trace, decode_program, pack_program
 from .levels import EnvLevels, LevelBank
+from .step_launch import StepPlan
 from .objects import COLOR_TO_IDX, OBJECT_TYPES, BonusTile, Box, Door, Goal, Key, Wall, WorldObj
 
 TILE_PIXELS = 32
@@ -481,36 +482,36 @@ class MultiGridEnv(object):
             raise ValueError("strict must be True, False or 'sync'")
         self.strict = strict
         self.obs_buffers = max(1, int(obs_buffers))
-        self.fused_step = bool(fused_step)     # step() = one launch (mg_step_render) instead of mg_step + mg_render_obs
+        # Which library call a step is follows from the options below: step_launch.py has the kinds, the order they are tried
+        # in, and what an MG_E_UNSUPPORTED does to it (`_plan`: chosen at the first step, remembered)
+        self._plan = StepPlan()
+        self._delta_launches = 0
+        self.fused_step = bool(fused_step)     # step() = one launch instead of mg_step + one launch per view group
         # encode_in_step=True: every step() (and reset()) also leaves `grid.encode()` of the batch — (B, W, H, 3) uint8,
-        # base.py:196-214 — in `self.grid_encoding`, written by the step's own launch where it can (mg_step_render_encode:
-        # +2.4 % bytes instead of a second launch), by an mg_encode launch behind it otherwise — also with episode_info /
-        # auto_reset="next_step": mg_step_render_encode has no _ep twin, the step is mg_step_render_ep and mg_encode follows
-        self.encode_in_step = bool(encode_in_step)
+        # base.py:196-214 — in `self.grid_encoding`, written by the step's own launch where it can (+2.4 % bytes instead of a
+        # second launch), by an mg_encode launch behind it otherwise
+        self.encode_in_step = encode_in_step
         self.grid_encoding = None
         # obs_format="encoded": reset() / step() / gen_obs() return every agent's gen_obs_grid(agent) -> grid.encode(vis_mask)
         # (base.py:418-451, 196-214) — (B, n, V, V, 3) uint8, index [i, j] — instead of the (B, n, P, P, 3) pixels; the step's
-        # launch writes them (mg_step_encode_views) and nothing is rasterised
+        # launch writes them and nothing is rasterised
         if obs_format not in ("image", "encoded"):
             raise ValueError("obs_format must be 'image' or 'encoded' (got %r)" % (obs_format,))
         self.obs_format = obs_format
         self._encoded = obs_format == "encoded"
-        self._enc_fused = True                 # until the library says MG_E_UNSUPPORTED for this configuration
-        self._ep_fused = True                  # the same for mg_step_render_ep
         # obs_delta: step() writes into a buffer set of the ring that still holds the observation of `obs_buffers` steps ago;
-        # with it the step's launch (mg_step_render_delta) compares, band by band — a tile row of an agent's image —, the tiles
+        # with it the step's launch compares, band by band — a tile row of an agent's image —, the tiles
         # it is about to draw with the ones that buffer was drawn from (a signature tensor kept per buffer set) and does not
         # store the bands that are the same: an agent that is blocked, done, or toggles / picks up / drops changes nothing.
         # The returned tensors are VIEWS of buffers the env owns: a caller that writes into them calls invalidate_obs() (or
         # constructs with obs_delta=False).  "auto": where the step is the one fused image launch without episode outputs or
         # encode_in_step and the library has an instantiation for the shape (view 7, 8-pixel tiles, <= 3 agents, none
         # 'prestige'); True: the same, but a configuration that cannot is an error — and ALSO with episode_info,
-        # auto_reset="next_step", encode_in_step or any mix of them (mg_step_render_delta_ex: the episode outputs, the grid
-        # encoding or both from the one delta launch; "auto" leaves those steps as they are); False: every step stores every byte.
+        # auto_reset="next_step", encode_in_step or any mix of them (the episode outputs, the grid encoding or both from the one
+        # delta launch; "auto" leaves those steps as they are); False: every step stores every byte.
         if obs_delta not in ("auto", True, False):
             raise ValueError("obs_delta must be 'auto', True or False (got %r)" % (obs_delta,))
         self.obs_delta = obs_delta
-        self._delta_ok = obs_delta is not False     # until the library says MG_E_UNSUPPORTED for this configuration
         # specialize: the library ships ~100 instantiations of the observation kernel; a (view_size, view_tile_size) pair off
         # that table runs the fully run-time one (the RuntimeWarning of _warn_generic_kernel), 2-2.4x slower.  "auto" / True: the
         # instantiation this configuration would have on the table is compiled when the env is built (mg_render_specialize: hipRTC,
@@ -742,7 +743,9 @@ class MultiGridEnv(object):
         return g.spec[want]
 
     def _release_spec(self):
-        """unload every handle (the tables changed: the instantiations were compiled for the old ones' LDS layout; or the env goes)"""
+        """unload every handle (the tables changed: the instantiations were compiled for the old ones' LDS layout; or the env goes)
+        — and with them the step's remembered call, which may hold one"""
+        self._plan.chosen = None
         for g in getattr(self, "_groups", ()):
             for h in g.spec.values():
                 if h:
@@ -799,7 +802,6 @@ class MultiGridEnv(object):
             # so that a captured step (torch.cuda.graph) sees an invalidation as an eager one does.  Made with the ring: step()
             # allocates nothing.
             self.episode_level = torch.full((B,), -1, dtype=torch.int64, device=dev)     # set_levels: the running episode's seed
-            self._delta_launches = 0
             if self._delta_wanted():
                 for r in self._ring:
                     r["sig"] = torch.full((B * N.delta_sig_bytes(n, self.view_size),), 0xFF, dtype=torch.uint8, device=dev)
@@ -1401,6 +1403,7 @@ class MultiGridEnv(object):
             return
         import torch
         self.invalidate_obs()               # (a tile index means other pixels once the atlas or the object table changes)
+        self._release_spec()                # (... and the `specialize` handles were compiled for the old tables)
         for g in self._groups:
             cfg, raw, flat, atlas = self._host_tables(g)
             # the obs kernel keeps 4 waves of per-env scratch (and the atlas, when it fits) in one workgroup's
@@ -1421,10 +1424,7 @@ class MultiGridEnv(object):
             name0 = N.render_kernel_name(cfg)[0] if raster_fits else ""
             # specialize: the group's plain instantiation is asked for now (nothing of cfg that lives on the device is looked at);
             # the atlas upload below follows the name of the kernel that will be launched
-            for h in g.spec.values():
-                if h:
-                    self._lib.mg_render_spec_release(h)
-            g.spec, g.spec_info, g.cfg = {}, {}, cfg
+            g.cfg = cfg
             if raster_fits and self._spec(g, N.WANT_PLAIN):
                 name0 = g.spec_info[N.WANT_PLAIN]["kernel_name"]
             if name0.endswith(", 2>") and not os.environ.get("MG_NO_GATHER_ATLAS"):
@@ -1594,110 +1594,25 @@ class MultiGridEnv(object):
         return self._package_obs(), self.rewards, done, info
 
     def _launch_step(self, actions, prog, stream, probe, ep):
-        """The step and the observations it returns: fused, if this configuration still can, else mg_step[_ep] and one launch
-        per view group; then mg_encode unless the launch wrote the encoding too.  `ep`: None, or the buffer set's MgEpisode
-        (episode_info and / or auto_reset="next_step") — every call is then the _ep twin of the one it would be."""
-        L, cfg, st = self._lib, C.byref(self._cfg), C.byref(self._state)
-        head = (cfg, st, actions.data_ptr(), actions.element_size(), self.rewards.data_ptr(), prog)
-        tail = (stream,) if ep is None else (ep, stream)
-        fused = self.fused_step and not self._hetero
-        encoding_written = False
-        rc = None       # the fused call's answer.  (MG_E_UNSUPPORTED: nothing was launched, this configuration has no such instantiation)
-        if self.obs_delta is True and (ep is not None or self.encode_in_step):
-            # obs_delta=True with episode outputs and / or encode_in_step: the delta launch that writes them too — with both, the
-            # one launch that has no non-delta twin (the table's path, like the plain delta: its one shape is on the table).
-            # A demand: an env whose step is not the fused image launch (view groups, fused_step=False, encoded views) raises
-            # here instead of stepping without it.
-            rc = self._launch_step_delta_ex(head, ep, stream)
-            encoding_written = self.encode_in_step
-        elif fused and self._encoded:
-            # the step and every agent's encoded view, one call
-            rc = (L.mg_step_encode_views if ep is None else L.mg_step_encode_views_ep)(*head, self.obs.data_ptr(), *tail)
-        elif fused and ep is not None:
-            # (there is no _ep twin of mg_step_render_encode: encode_in_step takes mg_step_render_ep + mg_encode)
-            h = self._spec(self._groups[0], N.WANT_EPISODE)
-            if h:
-                rc = L.mg_step_render_spec(h, *head, self.obs.data_ptr(), None, ep, stream)
-            elif self._ep_fused:
-                rc = L.mg_step_render_ep(*head, self.obs.data_ptr(), *tail)
-                if rc == N.E_UNSUPPORTED:
-                    self._ep_fused, rc = False, None
-        elif fused:
-            # the whole step — action loop, reset of finished episodes, observation raster — is ONE launch: the wave that
-            # renders an env steps it first; with encode_in_step it writes MultiGrid.encode of its envs too, unless there are
-            # more than 256 object ids + agent marks, or the grid is read in place, ...
-            # (specialize: through the group's own instantiation where it has one — with the encode: asked for at the first such step)
-            h = self._spec(self._groups[0], N.WANT_ENCODE) if self.encode_in_step else None
-            if h:
-                rc = L.mg_step_render_spec(h, *head, self.obs.data_ptr(), self._encoding_buffer().data_ptr(), None, stream)
-                encoding_written = True
-            elif self.encode_in_step and self._enc_fused:
-                rc = L.mg_step_render_encode(*head, self.obs.data_ptr(), self._encoding_buffer().data_ptr(), stream)
-                self._enc_fused = encoding_written = rc != N.E_UNSUPPORTED
-            if not encoding_written:
-                h = self._spec(self._groups[0], N.WANT_PLAIN)
-                rc = None
-                if h is None or self.obs_delta is True:      # (obs_delta keeps the table's path: its one shape is on the table)
-                    rc = self._launch_step_delta(head, stream)
-                if rc is None and h:
-                    rc = L.mg_step_render_spec(h, *head, self.obs.data_ptr(), None, None, stream)
-                elif rc is None:
-                    rc = L.mg_step_render(*head, self.obs.data_ptr(), stream)
-        if rc is not None:
-            N.check(rc)
-        else:
-            N.check((L.mg_step if ep is None else L.mg_step_ep)(*head, *tail))
-            if probe is not None:
-                probe(1)
-            self._launch_views()
-        if self.encode_in_step and not encoding_written:
-            self._encode_into(self._encoding_buffer())
+        """The step and the observations it returns, as whichever library call this env's step is (step_launch.py: chosen at
+        the first step, remembered).  `ep`: None, or the buffer set's MgEpisode (episode_info and / or auto_reset="next_step")."""
+        self._plan.launch(self, actions, prog, stream, probe, ep)
 
     def _delta_wanted(self):
-        """obs_delta: is this env's step the launch that has a delta twin (and has the library not said no yet)"""
-        if not (self._delta_ok and not self._encoded and self.fused_step and not self._hetero):
-            return False
-        # ("auto": the plain step alone; with episode outputs or encode_in_step only when asked for — obs_delta=True)
-        return self.obs_delta is True or not (self._use_ep or self.encode_in_step)
+        return self._plan.delta_wanted(self)
 
-    def _launch_step_delta(self, head, stream):
-        """mg_step_render_delta into the current buffer set.  Whether a band is stored is decided on the device alone, against
-        the set's signature (an invalidated one matches nothing): the call is the same whatever happened to the set, so a
-        captured step replays correctly after any invalidation.  None: not this configuration, nothing launched."""
-        r = self._ring[self._ring_i]
-        if not self._delta_wanted() or r["sig"] is None:
-            if self.obs_delta is True:
-                raise NotImplementedError("obs_delta=True needs the fused image step without view groups, and a shape the library "
-                                          "has a delta instantiation for (view 7 at 8-pixel tiles, at most 3 agents, no 'prestige' agent)")
-            return None
-        rc = self._lib.mg_step_render_delta(*head, self.obs.data_ptr(), r["sig"].data_ptr(), 0, stream)
-        if rc == N.E_UNSUPPORTED:
-            self._delta_ok = False
-            for q in self._ring:
-                q["sig"] = None
-            return self._launch_step_delta(head, stream)
-        self._delta_launches += 1
-        return rc
+    # what the library has not refused this env (read-only: the refusals are StepPlan's)
+    _enc_fused = property(lambda self: "enc" not in self._plan.refused)           # the fused render with the encode
+    _ep_fused = property(lambda self: "ep" not in self._plan.refused)             # ... with episode outputs
+    _delta_ok = property(lambda self: self.obs_delta is not False and "delta" not in self._plan.refused)
 
-    def _launch_step_delta_ex(self, head, ep, stream):
-        """mg_step_render_delta_ex into the current buffer set (obs_delta=True with episode outputs and / or encode_in_step): the
-        same signatures, the same invalidation points as _launch_step_delta.  obs_delta=True is a demand: a configuration the
-        library has no such instantiation for raises."""
-        r = self._ring[self._ring_i]
-        what = " + ".join(w for w, on in (("episode outputs", ep is not None), ("encode_in_step", self.encode_in_step)) if on)
-        if self._delta_wanted() and r["sig"] is not None:
-            enc = self._encoding_buffer().data_ptr() if self.encode_in_step else None
-            rc = self._lib.mg_step_render_delta_ex(*head, self.obs.data_ptr(), r["sig"].data_ptr(), 0, enc, ep, stream)
-            if rc != N.E_UNSUPPORTED:
-                self._delta_launches += 1
-                return rc
-            self._delta_ok = False      # (nothing was launched)
-            for q in self._ring:
-                q["sig"] = None
-        raise NotImplementedError("obs_delta=True with %s: no delta launch for this configuration — it needs the fused image step "
-                                  "(fused_step=True, obs_format='image', one view group), view 7 at 8-pixel tiles, at most 3 agents, "
-                                  "no 'prestige' agent, grid and atlas in LDS, and for encode_in_step at most 256 object kinds + "
-                                  "agent marks" % what)
+    @property
+    def encode_in_step(self):
+        return self._encode_in_step
+
+    @encode_in_step.setter
+    def encode_in_step(self, on):       # (the one option callers switch on a live env: its step may be another call from now on)
+        self._encode_in_step, self._plan.chosen = bool(on), None
 
     def invalidate_obs(self, buffer_set=None):
         """The observation tensors reset() / step() return are views of buffers the env owns and writes again `obs_buffers`

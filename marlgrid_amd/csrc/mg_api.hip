@@ -258,13 +258,14 @@ static int32_t step_render(const MgConfig* cfg, const MgState* st, const void* a
     const int e = check_step_args(cfg, st, actions, action_bytes, rewards, auto_reset, ep, true);
     if (e) return e;
     if (!obs) return MG_E_ARG;      // (every check between the state's and this one answers MG_E_ARG too)
+    // the one pick of the step: the launcher takes it as it is.  (A config without even a plain instantiation is the launcher's
+    // to refuse, as for mg_render_obs.)
+    const mg::RenderWant want = mg::render_want_of(sig != nullptr, encode_out != nullptr, ep != nullptr);
     mg::RenderPick pick;
-    if (sig) {      // (mg_step_render_delta; with the encode, the episode outputs or both: mg_step_render_delta_ex)
-        const mg::RenderWant want = encode_out && ep ? mg::kDeltaEncodeEpisode : ep ? mg::kDeltaEpisode : encode_out ? mg::kDeltaEncode : mg::kDelta;
-        if (!mg::render_pick(*cfg, want, &pick)) return MG_E_UNSUPPORTED;
-    } else if ((encode_out || ep) && !mg::render_pick(*cfg, ep ? mg::kEpisode : mg::kEncode, &pick)) return MG_E_UNSUPPORTED;
+    const bool picked = mg::render_pick(*cfg, want, &pick);
+    if (!picked && want != mg::kPlain) return MG_E_UNSUPPORTED;
     const mg::FusedStep fs = fused_step_of(cfg, actions, action_bytes, rewards, auto_reset, encode_out, ep, sig, sig_flags);
-    return rc(mg::launch_render(*cfg, *st, obs, nullptr, nullptr, nullptr, (hipStream_t)stream, &fs));
+    return rc(mg::launch_render(*cfg, *st, obs, nullptr, nullptr, nullptr, (hipStream_t)stream, &fs, picked ? &pick : nullptr));
 }
 
 // ... and through an instantiation compiled at run time (mg_rtc.hip: mg_render_specialize)

@@ -12,9 +12,12 @@ hipError_t launch_reset(const MgConfig& cfg, const MgState& st, const MgGenProgr
 hipError_t launch_step(const MgConfig& cfg, const MgState& st, const void* actions, int action_bytes,
                        float* rewards, const MgGenProgram* auto_reset, hipStream_t s, const MgEpisode* ep = nullptr);
 struct FusedStep;
-// (which instantiation a configuration gets, whether it has one with the encode / the episode code, its LDS: mg_render_pick.h)
+struct RenderPick;
+// (which instantiation a configuration gets, whether it has one with the encode / the episode code, its LDS: mg_render_pick.h;
+// `picked`: the caller's render_pick answer for this config and this step's want, where it has asked already)
 hipError_t launch_render(const MgConfig& cfg, const MgState& st, uint8_t* obs, uint8_t* view_cells,
-                         uint8_t* view_agent, uint8_t* vis_mask, hipStream_t s, const FusedStep* fused_step = nullptr);
+                         uint8_t* view_agent, uint8_t* vis_mask, hipStream_t s, const FusedStep* fused_step = nullptr,
+                         const RenderPick* picked = nullptr);
 // ... through a handle of mg_render_specialize (mg_rtc.hip); answers an MG_* code: MG_E_ARG when the handle was made for another shape
 int32_t launch_render_spec(void* handle, const MgConfig& cfg, const MgState& st, uint8_t* obs, hipStream_t s,
                            const FusedStep* fused_step);

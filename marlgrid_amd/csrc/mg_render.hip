@@ -73,18 +73,17 @@ static void render_override(const MgConfig& cfg, RenderPick& p) {
 
 // The kernel launch of mg_render_obs / mg_step_render / mg_step_render_encode / mg_step_render_ep / mg_step_render_delta[_ex].
 hipError_t launch_render(const MgConfig& cfg, const MgState& st, uint8_t* obs, uint8_t* view_cells,
-                         uint8_t* view_agent, uint8_t* vis_mask, hipStream_t s, const FusedStep* fused_step) {
+                         uint8_t* view_agent, uint8_t* vis_mask, hipStream_t s, const FusedStep* fused_step, const RenderPick* picked) {
     if (cfg.B <= 0) return hipSuccess;
     FusedStep fs{};                 // no step: the raster alone
     fs.action_bytes = 8;
     if (fused_step) fs = *fused_step;
-    // (the encode AND the episode outputs: under the delta alone — there is no non-delta instantiation with both)
-    const RenderWant want = fs.sig ? (fs.has_ep && fs.encode_out ? kDeltaEncodeEpisode : fs.has_ep ? kDeltaEpisode : fs.encode_out ? kDeltaEncode : kDelta)
-                                   : fs.has_ep ? kEpisode : fs.encode_out ? kEncode : kPlain;
+    const RenderWant want = render_want_of(fs.sig != nullptr, fs.encode_out != nullptr, fs.has_ep != 0);
     if (!fs.sig && fs.has_ep && fs.encode_out) return hipErrorInvalidValue;
     if ((view_cells || view_agent || vis_mask) && (want != kPlain || !(view_cells && view_agent && vis_mask))) return hipErrorInvalidValue;
     RenderPick p;
-    if (!render_pick(cfg, want, &p)) return want == kPlain ? hipErrorInvalidValue : hipErrorNotSupported;
+    if (picked) p = *picked;
+    else if (!render_pick(cfg, want, &p)) return want == kPlain ? hipErrorInvalidValue : hipErrorNotSupported;
     if (render_want_encode(want)) fs.enc_ne = render_enc_entries(cfg);
 #if defined(MG_AB_VARIANTS) || defined(MG_EXP) || defined(MG_DEV_ONLY)
     render_override(cfg, p);

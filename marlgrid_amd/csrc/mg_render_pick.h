@@ -203,6 +203,12 @@ enum RenderWant { kPlain, kEncode, kEpisode, kDelta, kDeltaEncode, kDeltaEpisode
 constexpr bool render_want_delta(RenderWant w) { return w >= kDelta; }
 constexpr bool render_want_encode(RenderWant w) { return w == kEncode || w == kDeltaEncode || w == kDeltaEncodeEpisode; }
 constexpr bool render_want_episode(RenderWant w) { return w == kEpisode || w == kDeltaEpisode || w == kDeltaEncodeEpisode; }
+// ... from what a launch was handed: a signature (the delta), an encode output, an MgEpisode.  (The encode AND the episode
+// outputs: under the delta alone — there is no non-delta instantiation with both, the launcher refuses that pair.)
+inline RenderWant render_want_of(bool sig, bool encode, bool episode) {
+    return sig ? (episode && encode ? kDeltaEncodeEpisode : episode ? kDeltaEpisode : encode ? kDeltaEncode : kDelta)
+               : episode ? kEpisode : encode ? kEncode : kPlain;
+}
 
 // dwords of the fused encode's LDS table — one per grid byte value, (n_obj + 4 n) rounded up to 16 —, 0: object ids and
 // agent marks do not share a byte, no fused encode

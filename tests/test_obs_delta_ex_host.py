@@ -195,13 +195,27 @@ class _Ptr:
     def data_ptr(self):
         return 64
 
+    def element_size(self):
+        return 8
+
 
 class _Refuses:
+    """a library that has mg_step_render_delta_ex alone, and refuses"""
     calls = 0
 
     def mg_step_render_delta_ex(self, *a):
         self.calls += 1
         return N.E_UNSUPPORTED
+
+
+def _dry_step(env, sig):
+    """-> a callable: one _launch_step of this dry env, with stand-ins for the tensors and a library that counts what it is asked"""
+    env._lib, env._ring, env._ring_i, env.obs, env.rewards = _Refuses(), [dict(sig=sig, ep=N.Episode())], 0, _Ptr(), _Ptr()
+    env._cfg, env._state = N.Config(), N.State()
+
+    def step():
+        env._launch_step(_Ptr(), None, None, None, C.byref(env._ring[0]["ep"]))
+    return step
 
 
 def test_true_raises_where_the_library_has_no_instantiation():
@@ -212,12 +226,13 @@ def test_true_raises_where_the_library_has_no_instantiation():
     agents = [dict(view_size=7, view_tile_size=5, observation_style="image", color=c) for c in ("red", "blue", "purple")]
     env = ClutteredMultiGrid(agents=agents, grid_size=15, n_clutter=20, batch_size=2, obs_delta=True, episode_info=True, _dry=True)
     assert env.tile_size == 5 and env._delta_wanted()          # construction: no error, nobody has said no yet
-    env._lib, env._ring, env._ring_i, env.obs, env._delta_launches = _Refuses(), [dict(sig=_Ptr())], 0, _Ptr(), 0
+    step = _dry_step(env, _Ptr())
     with pytest.raises(NotImplementedError, match="episode outputs.*8-pixel tiles"):
-        env._launch_step_delta_ex((None,) * 6, C.byref(N.Episode()), None)
+        step()
     assert env._lib.calls == 1 and not env._delta_wanted() and env._ring[0]["sig"] is None and env._delta_launches == 0
+    assert not env._delta_ok
     with pytest.raises(NotImplementedError):
-        env._launch_step_delta_ex((None,) * 6, C.byref(N.Episode()), None)
+        step()
     assert env._lib.calls == 1
 
 
@@ -228,7 +243,7 @@ def test_true_raises_off_the_fused_image_step(kw):
     from marlgrid_amd.envs import make
     env = make(NAME, batch_size=2, obs_delta=True, episode_info=True, _dry=True, **kw)
     assert not env._delta_wanted()
-    env._lib, env._ring, env._ring_i, env.obs, env._delta_launches = _Refuses(), [dict(sig=None)], 0, _Ptr(), 0
+    step = _dry_step(env, None)
     with pytest.raises(NotImplementedError, match="fused image step"):
-        env._launch_step_delta_ex((None,) * 6, C.byref(N.Episode()), None)      # (what _launch_step calls for this env: GPU test)
-    assert env._lib.calls == 0
+        step()
+    assert env._lib.calls == 0 and env._delta_launches == 0

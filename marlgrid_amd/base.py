@@ -40,8 +40,10 @@ from .gen_params import ParamTable
 from .goal import EnvGoal
 from .gen_recorder import GenDraw, GenRecorder, _NO_BRANCH, _any_draw, _gen_add, _trace, decode_program, pack_program
 from .levels import EnvLevels, LevelBank
+from . import launch_tables as LT
+from .launch_tables import _GENERIC_WARNED, _warn_generic_kernel      # noqa: F401  (tests reset the set through this module)
 from .step_launch import StepPlan
-from .objects import COLOR_TO_IDX, OBJECT_TYPES, BonusTile, Box, Door, Goal, Key, Wall, WorldObj
+from .objects import BonusTile, Goal, Wall, WorldObj
 
 TILE_PIXELS = 32
 DEFAULT_PLACE_OBS = "search"
@@ -382,42 +384,6 @@ def release_obs_cache(device=None):
     return N.lib().mg_obs_trim(idx)
 
 
-_GENERIC_WARNED = set()
-
-
-def _warn_generic_kernel(g, generic, prestige):
-    """mg_render_kernel_name's bits 1 | 2: view size AND tile size are run-time values of the launch — the fully generic
-    instantiation of the observation kernel (assemble-and-stream raster, run-time dividers, a 15-row shadow cast, 8- / 4-wave
-    workgroups), measured 2-2.4x slower than a specialised one (profiles/r05: view 9 at 5-pixel tiles 0.3136 -> 0.1360 ms
-    when it got its own).  Said once per configuration and process, naming what is specialised nearby."""
-    if generic != 3:
-        return
-    key = (g.view_size, g.tile_size, prestige, g.kernel_name)
-    if key in _GENERIC_WARNED:
-        return
-    _GENERIC_WARNED.add(key)
-    import warnings
-    if g.kernel_name.endswith(", 3>"):      # the grid-in-place variant: nothing about the view or the tiles would change it
-        warnings.warn("marlgrid_amd: this grid does not fit the observation kernel's LDS next to its per-cell agent maps (grids up "
-                      "to ~140 x 140, ~110 x 110 with hide_item_types, are staged there): it is read in place by the fully run-time "
-                      "instantiation (%s) — correct, every size up to 255 x 255, but slower per observation byte than a staged grid"
-                      % g.kernel_name, RuntimeWarning, stacklevel=4)
-        return
-    near = []
-    if prestige:
-        near.append("'prestige' agents: view_size 7 with any view_tile_size (5, 8 and 11 fastest), or view_tile_size 8 / 16 / 32 with any view")
-    else:
-        if g.view_size > 9:
-            near.append("view_size %d with view_tile_size 8, 16 or 32%s" % (g.view_size, ", or 5" if g.view_size in (11, 13, 15) else ""))
-        near.append("view_size 3 ... 9 with this view_tile_size (%d)" % g.tile_size)
-        if g.view_size not in (11, 13, 15):
-            near.append("view_size 11 / 13 / 15 with view_tile_size 5")
-    warnings.warn("marlgrid_amd: view_size=%d, view_tile_size=%d%s takes the fully run-time instantiation of the observation "
-                  "kernel (%s): correct, but 2-2.4x slower than a specialised one.  Specialised nearby: %s."
-                  % (g.view_size, g.tile_size, " with 'prestige' agents" if prestige else "", g.kernel_name, "; ".join(near)),
-                  RuntimeWarning, stacklevel=4)
-
-
 class _ViewGroup(object):
     """agents that share one view geometry: their launch config, atlas and observation buffers"""
 
@@ -563,7 +529,7 @@ class MultiGridEnv(object):
 
         self.obj_reg = ObjectRegistry()
         self._tables_version = -1
-        self._settings_seen = None
+        self._settings_seen = self._spawn_reject_key = None
         self._gen = GenRecorder(self)       # all `_gen_grid` recording state and logic (gen_recorder.py)
         self._prog_cache = {}
         self._params = ParamTable(self)     # the per-env parameters of `_gen_grid` (gen_params.py)
@@ -1249,215 +1215,62 @@ class MultiGridEnv(object):
     def place_agents(self, top=None, size=None, rand_dir=True, max_tries=1000):
         pass    # deprecated no-op upstream as well (base.py:710-712)
 
-    # ---- tables: object descriptors + atlas -----------------------------------------------------------
+    # ---- tables: object descriptors, atlas, settings — derived in launch_tables.py, uploaded here -------
     def _obj_table(self, tile_size=None):
-        tile_size = self.tile_size if tile_size is None else tile_size
-        objs = self.obj_reg.objs
-        tab = (N.ObjDesc * len(objs))()
-        for i, o in enumerate(objs):
-            if o is None:
-                continue
-            d = tab[i]
-            t, c, s = o.encode()
-            d.type_idx, d.color_idx, d.state = t, c, s
-            f = 0
-            f |= N.OF_CAN_OVERLAP if o.can_overlap() else 0
-            f |= N.OF_CAN_PICKUP if o.can_pickup() else 0
-            f |= N.OF_SEE_BEHIND if o.see_behind() else 0
-            f |= N.OF_ENDS_EPISODE if o.ends_episode else 0
-            f |= N.OF_IS_KEY if isinstance(o, Key) else 0
-            f |= N.OF_IS_BOX if isinstance(o, Box) else 0
-            if isinstance(o, Door):
-                f |= N.OF_IS_DOOR
-                if o.state == Door.LOCKED:
-                    f |= N.OF_DOOR_LOCKED
-                d.unlock_next = self.obj_reg.find(Door(o.color, Door.CLOSED))
-                d.toggle_next = self.obj_reg.find(Door(o.color, Door.OPEN if o.state == Door.CLOSED else Door.CLOSED))
-            d.flags = f
-            try:    # "a corner of the plain tile is black" (the border rule of render_tile, base.py:296-298)
-                plain = rendering.render_sprite(o.sprite_ops(), tile_size)
-            except NotImplementedError:
-                plain = np.zeros((tile_size, tile_size, 3), np.uint8)
-            d.flags2 = int((plain[[0, 0, -1, -1], [0, -1, 0, -1]] == 0).all(axis=-1).any())
-            if isinstance(o, Goal):
-                d.reward_kind, d.reward = 1, float(o.reward)
-            elif isinstance(o, BonusTile):
-                d.reward_kind, d.reward, d.penalty = 2, float(o.reward), float(o.penalty)
-                d.bonus_id, d.n_bonus = o.bonus_id, o.n_bonus
-                d.bonus_flags = (1 if o.initial_reward else 0) | (2 if o.reset_on_mistake else 0)
-        return tab
+        return LT.obj_table(self.obj_reg, self.tile_size if tile_size is None else tile_size)
 
     def _host_tables(self, group=None):
-        """Everything the kernels need that is derived on the host from the object registry and the agent
-        interfaces, for one view group (default: the first): (cfg without device pointers, object table
-        bytes, atlas bytes, atlas array).  Pure host work (no device access) — the upload is `_sync_tables`."""
+        """(cfg without pointers, object table bytes, atlas bytes, atlas) of a view group (default: the first); hide_by goes on the group"""
         grp = self._groups[0] if group is None else group
-        objs = self.obj_reg.objs
-        atlas, ovl_slot, n_slots = rendering.build_atlas(objs, [a.color for a in self.agents], grp.tile_size,
-                                                         prestige_sprites=any(self._prestige))
-        tab = self._obj_table(grp.tile_size)
-        for i in range(len(objs)):
-            tab[i].ovl_slot = ovl_slot[i]
-        raw = np.frombuffer(bytes(tab), dtype=np.uint8).copy()
-        flat = atlas.reshape(-1)
-        pad = (-flat.size) % 16
-        flat = np.concatenate([flat, np.zeros(pad + 16, np.uint8)])
-        cfg = N.Config()
-        cfg.B, cfg.W, cfg.H, cfg.n_agents = self.batch_size, self.width, self.height, self.num_agents
-        cfg.view_size, cfg.tile_size = grp.view_size, grp.tile_size
-        cfg.view_offset, cfg.see_through_walls = grp.view_offset, int(grp.see_through_walls)
-        if self._hetero:                       # this group's agents only are rendered with this geometry
-            cfg.n_view = len(grp.members)
-            for i, k in enumerate(grp.members):
-                cfg.view_agent[i] = k
-        cfg.cells_stride = self.cells_stride
-        cfg.n_obj, cfg.n_ovl_slots, cfg.n_tiles = len(objs), n_slots, atlas.shape[1]
-        cfg.agent_type_idx = OBJECT_TYPES.index(GridAgentInterface)
-        for k, a in enumerate(self.agents):
-            cfg.agent_color_idx[k] = COLOR_TO_IDX[a.color]
-        # 'prestige' agents (agents.py:92-119, 141-153): per-env recoloured sprites
-        for k, a in enumerate(self.agents):
-            if self._prestige[k]:
-                cfg.prestige_mask |= 1 << k
-        if cfg.prestige_mask:
-            cfg.prestige_sprite_tile = atlas.shape[1] - 4
-            for d in range(4):      # max alpha of the (white) sprite per dir = max of blend_tiles' alpha map
-                cfg.prestige_amax[d] = int(atlas[0, atlas.shape[1] - 4 + d][..., 0].max())
-        # hide_item_types (base.py:441-449): per object id the agents that hide its type (bit k = agent k; a device table,
-        # uploaded by _sync_tables), and the agents that hide 'Agent'
-        hide_by = np.zeros(len(objs), np.uint32)
-        for k, a in enumerate(self.agents):
-            for i, o in enumerate(objs):
-                if o is not None and o.type in a.hide_item_types:
-                    hide_by[i] |= np.uint32(1 << k)
-            if "Agent" in a.hide_item_types:
-                cfg.hide_agent_mask |= 1 << k
-        grp.hide_by = hide_by if hide_by.any() else None
-        cfg.any_hide = int(cfg.hide_agent_mask != 0 or bool(hide_by.any()))
-        self._refresh_cfg(cfg)
-        return cfg, raw, flat, atlas
+        *tables, grp.hide_by = LT.group_tables(self, grp)
+        return tuple(tables)
+
+    _spawn_reject = property(lambda self: LT.reject_table(self, LT.read_settings(self)))     # read-only: the spawn's reject_fn as a table
 
     def _refresh_cfg(self, cfg):
-        """The scalar settings the reference reads on every step (max_steps, reward_decay, ghost_mode,
-        respawn, agent_spawn_kwargs, the agents' spawn_delay / prestige parameters): copied into the
-        launch config before every launch, so changing the attribute between steps takes effect on the
-        next step, as upstream."""
-        cfg.max_steps, cfg.reward_decay = int(self.max_steps), int(bool(self.reward_decay))
-        # upstream tests `ghost_mode is False` when moving (base.py:541) but `not ghost_mode` when placing
-        # (base.py:683): they differ for falsy non-False values such as 0 or None
-        cfg.ghost_mode = (1 if self.ghost_mode is not False else 0) | (2 if self.ghost_mode else 0)
-        cfg.respawn = int(bool(self.respawn))
-        # place_obj(agent, **agent_spawn_kwargs) (base.py:411, 505, 643)
-        kw = dict(self.agent_spawn_kwargs or {})
-        reject_fn = kw.pop("reject_fn", None)
-        top, size, max_tries = kw.pop("top", None), kw.pop("size", None), kw.pop("max_tries", 1e5)
-        if kw:
-            raise TypeError("place_obj() got an unexpected keyword argument %r" % sorted(kw)[0])
-        cfg.spawn_x0, cfg.spawn_y0, cfg.spawn_x1, cfg.spawn_y1 = self._place_region(top, size)
-        # agent_spawn_kwargs['reject_fn'] (base.py:411, 505, 643 -> :700-701): tabulated like place_obj's
-        self._spawn_reject = self._reject_table(reject_fn, (cfg.spawn_x0, cfg.spawn_y0, cfg.spawn_x1, cfg.spawn_y1))
-        if self._spawn_reject is not None and not self._dry:
-            if getattr(self, "_spawn_reject_key", None) != self._spawn_reject.tobytes():
-                self._spawn_reject_dev = self._table_dev(self._spawn_reject)
-                self._spawn_reject_key = self._spawn_reject.tobytes()
-            cfg.spawn_reject = self._spawn_reject_dev.data_ptr()
-        else:
-            cfg.spawn_reject = None
-        cfg.spawn_max_tries = int(max(1, min(max_tries, 1e5)))
-        for k, a in enumerate(self.agents):
-            if a.spawn_delay < 0:
-                raise ValueError("spawn_delay must be >= 0")
-            cfg.spawn_delay[k] = int(a.spawn_delay)
-            cfg.prestige_beta[k], cfg.prestige_scale[k] = float(a.prestige_beta), float(a.prestige_scale)
-        cfg.any_spawn_delay = int(any(a.spawn_delay != 0 for a in self.agents))
-
-    def _settings_key(self):
-        """the attributes _refresh_cfg reads, as one comparable value (what step() checks instead of re-deriving
-        every launch config on every step)"""
-        kw = self.agent_spawn_kwargs
-
-        def plain(v):       # array-likes by value (an ndarray has no truth value to compare with), callables by identity
-            if callable(v):
-                return ("fn", id(v))
-            if isinstance(v, (list, tuple)) or hasattr(v, "tolist"):
-                return tuple(np.asarray(v).reshape(-1).tolist())
-            return v
-        # the DERIVED values where upstream distinguishes more than == does: `ghost_mode is False` (base.py:541)
-        # against `not ghost_mode` (base.py:683) — False and 0 compare equal and configure different engines
-        return (int(self.max_steps), bool(self.reward_decay), self.ghost_mode is not False, bool(self.ghost_mode),
-                bool(self.respawn), bool(self.auto_reset),
-                tuple(sorted((k, plain(v)) for k, v in kw.items())) if kw else (),
-                tuple((a.spawn_delay, a.prestige_beta, a.prestige_scale) for a in self.agents))
+        LT.apply_settings(cfg, LT.read_settings(self), cfg.spawn_reject)
 
     def _sync_tables(self):
-        """Make the launch configs current: rebuild and upload the object table / atlas of every view group
-        when a new object kind was registered since the last launch, refresh the scalar settings always."""
+        """Make the launch configs current: rebuild and upload the object table / atlas of every view group when a new
+        object kind was registered since the last launch, apply the scalar settings when their value (LT.read_settings) changed."""
         if self._dry:
             return
-        if self._tables_version == self.obj_reg.version:
-            key = self._settings_key()
-            if key != self._settings_seen:
-                for g in self._groups:
-                    self._refresh_cfg(g.cfg)
-                self._settings_seen = key
+        settings = LT.read_settings(self)
+        stale = self._tables_version != self.obj_reg.version
+        if not stale and settings == self._settings_seen:
             return
-        import torch
-        self.invalidate_obs()               # (a tile index means other pixels once the atlas or the object table changes)
-        self._release_spec()                # (... and the `specialize` handles were compiled for the old tables)
+        rej = LT.reject_table(self, settings)       # (tabulated once for the env; uploaded when the table changed)
+        if rej is not None and self._spawn_reject_key != rej.tobytes():
+            self._spawn_reject_dev, self._spawn_reject_key = self._table_dev(rej), rej.tobytes()
+        if stale:
+            import torch
+            self.invalidate_obs()               # (a tile index means other pixels once the atlas or the object table changes)
+            self._release_spec()                # (... and the `specialize` handles were compiled for the old tables)
+            for g in self._groups:
+                t = LT.group_tables(self, g)
+                g.cfg, g.atlas, flat = t.cfg, t.atlas, t.atlas_flat
+                fits = LT.raster_fits(g.cfg, self._encoded)
+                # specialize: the group's plain instantiation is asked for now; the atlas follows the name of the kernel to be launched
+                name, generic = N.render_kernel_name(g.cfg) if fits else ("", 0)
+                if fits and self._spec(g, N.WANT_PLAIN):
+                    name, generic = g.spec_info[N.WANT_PLAIN]["kernel_name"], 0
+                if name.endswith(", 2>"):
+                    flat, g.cfg.atlas_gather_off = LT.gather_atlas(flat, g.cfg.n_tiles, g.tile_size)
+                g.obj_dev = torch.from_numpy(t.obj_raw).to(self.device)
+                g.atlas_dev = torch.from_numpy(flat).to(self.device)
+                g.hide_dev = None if t.hide_by is None else torch.from_numpy(t.hide_by.view(np.int32)).to(self.device)
+                g.cfg.obj, g.cfg.atlas = g.obj_dev.data_ptr(), g.atlas_dev.data_ptr()
+                g.cfg.hide_by_obj = None if g.hide_dev is None else g.hide_dev.data_ptr()
+                # the launcher's pick for this group (what rocprofv3 will call the launch); a warning when it is the fully generic one
+                if self._encoded:
+                    name, generic = "mg::encode_views_kernel<%d>" % (g.view_size if g.view_size in (5, 7, 9) else 0), 0
+                g.kernel_name = name
+                _warn_generic_kernel(g, generic, bool(g.cfg.prestige_mask))
         for g in self._groups:
-            cfg, raw, flat, atlas = self._host_tables(g)
-            # the obs kernel keeps 4 waves of per-env scratch (and the atlas, when it fits) in one workgroup's
-            # LDS: ask the library, which owns that layout, before anything is uploaded
-            need = N.lib().mg_render_obs_lds_bytes(C.byref(cfg))
-            raster_fits = 0 <= need <= 160 * 1024
-            if not raster_fits and not self._encoded:      # (encoded views have no per-env pixel scratch)
-                raise NotImplementedError(
-                    "this configuration needs %d KiB of LDS per workgroup for 4 waves of per-env scratch; the obs "
-                    "kernel has 160 KiB — with 'prestige' agents reduce their number or the tile size (every one of them has "
-                    "its four recoloured sprites there); otherwise the number of agents / the view size" % (need // 1024))
-            g.obj_dev = torch.from_numpy(raw).to(self.device)
-            # the gather instantiations (raster 2: 5-, 6-, 7-, 9- ... 12-pixel tiles; examples/human_player.py's shape) take the atlas
-            # in the raster's own LDS layout when the host has it ready — behind the plain one, `atlas_gather_off` bytes on —: building
-            # it per workgroup was 5 us of human_player's 130 us launch (20 instructions per dword, 45 dwords per thread), 1 - 1.6 %
-            # of the others'
-            cfg.atlas_gather_off = 0
-            name0 = N.render_kernel_name(cfg)[0] if raster_fits else ""
-            # specialize: the group's plain instantiation is asked for now (nothing of cfg that lives on the device is looked at);
-            # the atlas upload below follows the name of the kernel that will be launched
-            g.cfg = cfg
-            if raster_fits and self._spec(g, N.WANT_PLAIN):
-                name0 = g.spec_info[N.WANT_PLAIN]["kernel_name"]
-            if name0.endswith(", 2>") and not os.environ.get("MG_NO_GATHER_ATLAS"):
-                ts, seg = g.tile_size, 3 * g.tile_size
-                rs = (16 + seg + 3) // 4 * 4
-                rows = np.ascontiguousarray(flat[:4 * cfg.n_tiles * ts * seg]).reshape(-1, seg)
-                padded = np.zeros((rows.shape[0], rs), np.uint8)
-                padded[:, 16:16 + seg] = rows
-                pb = np.concatenate([padded.reshape(-1), np.zeros(32, np.uint8)])
-                pb = np.concatenate([pb, np.zeros((-pb.size) % 16, np.uint8)])
-                off = (flat.size + 15) // 16 * 16
-                flat = np.concatenate([flat, np.zeros(off - flat.size, np.uint8), pb])
-                cfg.atlas_gather_off = off
-            g.atlas_dev = torch.from_numpy(flat).to(self.device)
-            g.atlas = atlas
-            cfg.obj, cfg.atlas = g.obj_dev.data_ptr(), g.atlas_dev.data_ptr()
-            g.hide_dev = None if g.hide_by is None else torch.from_numpy(g.hide_by.view(np.int32)).to(self.device)
-            cfg.hide_by_obj = None if g.hide_dev is None else g.hide_dev.data_ptr()
-            g.cfg = cfg
-            # which instantiation of the observation kernel the launcher picks for this group (what rocprofv3 will call the
-            # launch) — and a warning, once per configuration, when it is the fully generic one
-            if self._encoded:
-                g.kernel_name = "mg::encode_views_kernel<%d>" % (g.view_size if g.view_size in (5, 7, 9) else 0)
-            else:
-                g.kernel_name, generic = N.render_kernel_name(cfg)
-                if g.spec.get(N.WANT_PLAIN):
-                    g.kernel_name = g.spec_info[N.WANT_PLAIN]["kernel_name"]
-                else:
-                    _warn_generic_kernel(g, generic, bool(cfg.prestige_mask))
+            LT.apply_settings(g.cfg, settings, None if rej is None else self._spawn_reject_dev.data_ptr())
         g0 = self._groups[0]
         self._cfg, self.atlas, self._obj_dev, self._atlas_dev = g0.cfg, g0.atlas, g0.obj_dev, g0.atlas_dev
-        self._tables_version = self.obj_reg.version
-        self._settings_seen = self._settings_key()
+        self._tables_version, self._settings_seen = self.obj_reg.version, settings
 
     def _program(self, template, ops):
         import torch

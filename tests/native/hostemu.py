@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 
 from marlgrid_amd import _native as N
+from marlgrid_amd import launch_tables as LT
 from marlgrid_amd import seeding
 from marlgrid_amd.gen_recorder import pack_program       # the product's own packing, with its range asserts
 
@@ -70,18 +71,20 @@ class HostEmu(object):
 
     def _cfg(self):
         env = self.env
+        settings = LT.read_settings(env)
         if self._tables_version != env.obj_reg.version:
-            self.cfg, self._obj_raw, _, _ = env._host_tables()
+            t = LT.group_tables(env, env._groups[0])
+            self.cfg, self._obj_raw, self._hide_by = t.cfg, t.obj_raw, t.hide_by
             self.cfg.obj = self._obj_raw.ctypes.data
-            self._hide_by = env._groups[0].hide_by
             self.cfg.hide_by_obj = None if self._hide_by is None else self._hide_by.ctypes.data
-            self._tables_version = env.obj_reg.version
-        else:
-            env._refresh_cfg(self.cfg)
-        if getattr(env, "_spawn_reject", None) is not None:     # agent_spawn_kwargs['reject_fn'], tabulated
-            self._spawn_rej = np.zeros(env.cells_stride, np.uint8)
-            self._spawn_rej[:env.width * env.height] = env._spawn_reject.reshape(-1)
-            self.cfg.spawn_reject = self._spawn_rej.ctypes.data
+            self._tables_version, self._settings = env.obj_reg.version, None
+        if settings != self._settings:
+            rej = LT.reject_table(env, settings)                # agent_spawn_kwargs['reject_fn'], tabulated
+            self._spawn_rej = None if rej is None else np.zeros(env.cells_stride, np.uint8)
+            if rej is not None:
+                self._spawn_rej[:env.width * env.height] = rej.reshape(-1)
+            LT.apply_settings(self.cfg, settings, None if rej is None else self._spawn_rej.ctypes.data)
+            self._settings = settings
         return self.cfg
 
     def _prog(self, trace):

@@ -542,3 +542,44 @@ def test_obs_ring_longer_than_a_placement_call():
     assert len(seen) == 9
     del env, twin
     gc.collect()
+
+
+def _spawn_reject_row(pos):
+    return pos[0] == 2
+
+
+def test_a_setting_assigned_later_equals_the_constructor_value():
+    """every scalar setting the launch config carries (marlgrid_amd/launch_tables.py: read_settings): an env constructed with
+    the value and an env constructed with the default and ASSIGNED the value afterwards run the same episodes — grids, agent
+    records, rewards, done and observations equal over seed(); reset() and 12 steps of the same actions"""
+    import torch
+    from marlgrid_amd.agents import GridAgentInterface
+    Env = product_envs._spawn_rect_env_class()          # (its `_gen_grid` leaves agent_spawn_kwargs alone)
+    B, T = 64, 12
+
+    def make(env_kw={}, agent_kw={}):
+        team = [GridAgentInterface(color=c, view_size=7, view_tile_size=8, **agent_kw.get(k, {}))
+                for k, c in enumerate(("red", "blue", "prestige"))]
+        return Env(agents=team, grid_size=9, batch_size=B, place_obs=False, **env_kw)
+    rows = [("env", dict(max_steps=5)), ("env", dict(reward_decay=False)), ("env", dict(ghost_mode=False)),
+            ("env", dict(ghost_mode=0)), ("env", dict(ghost_mode=None)), ("env", dict(respawn=True)),
+            ("env", dict(agent_spawn_kwargs=dict(top=(1, 1), size=(3, 3)))), ("env", dict(agent_spawn_kwargs=dict(max_tries=20))),
+            ("env", dict(agent_spawn_kwargs=dict(reject_fn=_spawn_reject_row))),
+            (1, dict(spawn_delay=3)), (2, dict(prestige_beta=0.5)), (2, dict(prestige_scale=3))]
+    actions = torch.randint(0, 7, (T, B, 3), generator=torch.Generator().manual_seed(11))
+    for where, kw in rows:
+        a = make(env_kw=kw) if where == "env" else make(agent_kw={where: kw})
+        b = make()
+        for name, v in kw.items():
+            setattr(b if where == "env" else b.agents[where], name, v)
+        outs = []
+        for env in (a, b):
+            env.seed(77)
+            out = [env.reset().clone()]
+            for t in range(T):
+                o, r, d, _ = env.step(actions[t])
+                out += [o.clone(), r.clone(), d.clone(), env.grid_state.clone(), env.agent_state.clone(), env.prestige_t.clone()]
+            outs.append(out)
+        assert len(outs[0]) == len(outs[1]) == 1 + 6 * T
+        for k, (x, y) in enumerate(zip(*outs)):
+            assert torch.equal(x, y), (kw, k)

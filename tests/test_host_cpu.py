@@ -125,8 +125,9 @@ def test_reject_fn_is_recorded_as_tables():
     assert [(o[0], o[1]) for o in ops] == [(1, 5), (3, 1)] and all(o[7] is not None for o in ops)
     t = np.frombuffer(ops[1][7], np.uint8).reshape(9, 9)
     assert sorted(map(tuple, np.argwhere(t))) == [(1, 1), (2, 2), (3, 3), (4, 4)]
-    env._host_tables()             # (derives the launch config on the host: what a non-dry env does before a launch)
-    assert env._spawn_reject is not None and env._spawn_reject[:, :4].all() and not env._spawn_reject[:, 4:].any()
+    from marlgrid_amd import launch_tables as LT
+    spawn_reject = LT.reject_table(env, LT.read_settings(env))      # (what a non-dry env tabulates and uploads before a launch)
+    assert spawn_reject is not None and spawn_reject[:, :4].all() and not spawn_reject[:, 4:].any()
     # a callback that rejects every cell of the rectangle is a RecursionError at run time, not here; an unknown
     # keyword in agent_spawn_kwargs still is a TypeError, as place_obj(**kw) would raise upstream
     env.agent_spawn_kwargs = dict(reject=lambda p: False)

@@ -1593,8 +1593,8 @@ class MultiGridEnv(object):
     def check_agent_position_integrity(self, title=""):
         """base.py:479-499 checks that every agent is in the grid exactly once (stack handling is
         error-prone there).  The packed records cannot express an agent in two places; what can be
-        checked is that they are consistent: placed agents are inside the grid on a cell an agent
-        can stand on, stack ranks are a permutation, active implies placed.  Raises AssertionError
+        checked is that they are consistent: placed agents are inside the grid on a cell that can
+        hold agents (one they overlap, or a door that was shut on them), stack ranks are a permutation, active implies placed.  Raises AssertionError
         (the reference drops into pdb)."""
         import torch
         pos, fl, rk = self.agent_pos, self.agent_flags, self.agent_rank
@@ -1602,8 +1602,8 @@ class MultiGridEnv(object):
         ok = ~placed | ((pos[..., 0] < self.width) & (pos[..., 1] < self.height))
         cell = (pos[..., 0] * self.height + pos[..., 1]).clamp(max=self.width * self.height - 1)
         base = torch.gather(self.grid_state[:, :self.width * self.height].long(), 1, cell)
-        overlap = torch.tensor([True] + [bool(o.can_overlap()) for o in self.obj_reg.objs[1:]], device=self.device)
-        ok &= ~placed | overlap[base]
+        holds = torch.tensor([True] + [bool(o.can_hold_agents()) for o in self.obj_reg.objs[1:]], device=self.device)
+        ok &= ~placed | holds[base]
         ok &= ((fl & N.AF_ACTIVE) == 0) | placed
         ok &= (rk.sort(dim=1).values == torch.arange(self.num_agents, device=self.device)).all(dim=1, keepdim=True)
         if not bool(ok.all()):

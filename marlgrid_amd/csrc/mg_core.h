@@ -877,6 +877,9 @@ MG_HD StepCtx step_begin(const MgConfig& cfg, const MgState& st, int b, const St
     return c;
 }
 
+// whether an agent standing in a cell whose base object is `base` may leave it: nothing there, or something it overlaps
+MG_HD bool cell_lets_go(const uint8_t* oflags, uint32_t base) { return base == 0 || (oflags[base] & MG_OF_CAN_OVERLAP) != 0; }
+
 MG_HD void step_agents(const MgConfig& cfg, const MgState& st, float* rewards, int b, const StepScratch& sc, uint8_t* g, StepCtx& c) {
     const int n = cfg.n_agents, W = cfg.W, H = cfg.H, S = sc.S, col = sc.col;
     uint64_t* s_rec = sc.rec;
@@ -924,6 +927,11 @@ MG_HD void step_agents(const MgConfig& cfg, const MgState& st, float* rewards, i
                                               : (agents_on(s_rec, S, col, n, (uint32_t)cx | ((uint32_t)cy << 8)) ? MG_ERR_VALUE : MG_ERR_ATTRIBUTE);
                             err = err ? err : e2;
                         } else if (can_move) {
+                            // a door was shut on the agent standing in it (Door.toggle closes whoever is inside,
+                            // objects.py:344-345): `assert cur_cell.can_overlap()` (base.py:558).  Upstream the agent is
+                            // in its new cell by then (:547-552); the error is recorded and the move completes — what
+                            // the env holds after an error is not upstream's state in any case
+                            if (!cell_lets_go(sc.oflags, g[cx * H + cy])) err = err ? err : MG_ERR_ASSERT;
                             r = arrive(s_rec, S, col, n, r);
                             r = rec_set(r, MG_AG_X, (uint32_t)fx);
                             r = rec_set(r, MG_AG_Y, (uint32_t)fy);
@@ -1121,6 +1129,7 @@ MG_HD ParLane step_par_resolve(const MgConfig& cfg, const StepScratch& sc, const
             else if (action == 2) {
                 const bool can_move = fbase ? (fflags & MG_OF_CAN_OVERLAP) != 0 : true;
                 if (can_move && (flags & MG_AF_EVICTED)) serial = true;
+                if (can_move && !cell_lets_go(sc.oflags, g[cx * H + cy])) serial = true;     // AssertionError: the loop records it
                 if (can_move && !(cfg.ghost_mode & 1) && fbase == 0) {
                     // blocked iff an agent stands there WHEN THIS AGENT ACTS (base.py:541-542): nobody there now and nobody
                     // heading there -> free whatever the order; anything else is the loop's business

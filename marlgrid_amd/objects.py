@@ -77,6 +77,10 @@ class WorldObj(metaclass=_Registered):
     def can_pickup(self):
         return self.pickable
 
+    def can_hold_agents(self):
+        """whether agents can be in this object's `agents` list: they walked in — or the object changed under them (Door)"""
+        return self.can_overlap()
+
     def see_behind(self):
         return self.transparent
 
@@ -225,6 +229,11 @@ class Door(WorldObj):
 
     def see_behind(self):
         return self.state == self.OPEN
+
+    def can_hold_agents(self):
+        # Door.toggle shuts an open door whoever stands in it (objects.py:344-345): the closed door keeps its agents, and
+        # render_tile blends the first of them over it like over any object (base.py:288-294).  Nothing becomes LOCKED.
+        return self.state in (self.OPEN, self.CLOSED)
 
     def related(self):
         return [Door(self.color, s) for s in (1, 2, 3) if s != self.state]

@@ -127,7 +127,7 @@ def build_atlas(objects, agent_colors, ts, prestige_sprites=False):
     ovl_slot[0] = 0
     n_slots = 1
     for i, o in enumerate(objects):
-        if o is not None and o.can_overlap():
+        if o is not None and o.can_hold_agents():
             ovl_slot[i] = n_slots
             n_slots += 1
     n_tiles = 1 + n_obj + n_slots * n_ag * 4 + (4 if prestige_sprites else 0)

@@ -50,6 +50,16 @@ class Plan(object):
         a[self.probed, 0] = FORWARD
         return a
 
+    def errors(self, grid, env, pos):
+        """the error word every env has to hold after the probe step, (B,): ERR_ASSERT exactly where the probe stood in a cell
+        whose object does not let an agent overlap — a wall, say — and moved out of it (`assert cur_cell.can_overlap()`,
+        base.py:558: the step records the error and completes the move, so the verdict is read all the same), 0 elsewhere.
+        grid (W, H): the probed grid's object ids; env: whose registry knows the kinds; pos (B, 2): agent 0 after the step"""
+        lets_go = np.array([True] + [bool(o.can_overlap()) for o in env.obj_reg.objs[1:]])[np.asarray(grid)]
+        pos = np.asarray(pos)
+        moved = (pos[:, 0] == self.cx) & (pos[:, 1] == self.cy)
+        return np.where(self.probed & moved & ~lets_go[self.x, self.y], N.ERR_ASSERT, 0)
+
     def verdicts(self, pos, done, rew):
         """agent 0 after the step — pos (B, 2), done (B,) its DONE flag, rew (B,) its reward — -> (verdict (W, H) of BLOCKED /
         FREE / GOAL, counts (moved, ended, paid) over the probes).  Every cell is entered by a probe, and the probes agree."""

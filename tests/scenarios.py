@@ -152,6 +152,7 @@ def ref_recipe(name):
         "Test-3AgentEmpty7x11-nonsquare": ("EmptyMultiGrid", dict(width=7, height=11)),
         "Test-3AgentCluttered12x6-nonsquare": ("ClutteredMultiGrid", dict(width=12, height=6, n_clutter=7)),
         "Test-2AgentEmpty9x7-zoo": ("EmptyMultiGrid", dict(width=9, height=7)),
+        "Test-3AgentEmpty9x9-acttable": ("EmptyMultiGrid", dict(grid_size=9, max_steps=1000)),
         "Test-2AgentLateStatic10x10": ("LateStaticTestEnv", dict(grid_size=10, respawn=True, max_steps=50)),
         "Limit-24AgentEmpty20x20-view5": ("EmptyMultiGrid", dict(grid_size=20, max_steps=60)),
         "Limit-3Agent100Kinds24x24": ("KindsTestEnv", dict(grid_size=24, max_steps=80)),
@@ -448,6 +449,8 @@ def registered(name):   # noqa: F811  (extends the table above with test-only sc
         "Test-3AgentCluttered12x6-nonsquare": lambda: cluttered_spec(3, 12, 5, n_clutter=7, H=6),
         # the board tests/goal_probe.py puts one object of every kind on (the step-probed cell kinds of goal_distance)
         "Test-2AgentEmpty9x7-zoo": lambda: empty_spec(2, 9, 7, H=7, colors=["red", "cyan"]),
+        # the room of tests/act_table.py (pickup / drop / toggle, case by case): its objects are written in after the reset
+        "Test-3AgentEmpty9x9-acttable": lambda: empty_spec(3, 9, 7, colors=["red", "cyan", "purple"], max_steps=1000),
         "Edge-3AgentCluttered15x15-default-tiles": lambda: cluttered_spec(3, 15, 7, n_clutter=10, tile_size=5,
                                                                           colors=["red", "red", "red"]),
         "Edge-3AgentCluttered11x11-offset6": lambda: cluttered_spec(3, 11, 7, n_clutter=12, view_offset=6),

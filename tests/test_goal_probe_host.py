@@ -45,8 +45,9 @@ def _probe(name, par, prepare=None):
     fields = _fields(emu)
     emu.rec[:, 0] = plan.records(emu.rec[:, 0])
     rew, _ = emu.step(plan.actions(emu.n))
-    assert (emu.error == 0).all()
     pos, _, fl = G.unpack_records(emu.rec)
+    want_err = plan.errors(grid[0], emu.env, pos[:, 0])
+    assert np.array_equal(emu.error, want_err) and (want_err != 0).any() and (want_err == 0).any()
     assert np.array_equal(pos[~plan.probed, 0], pos0[~plan.probed, 0])
     verdict, counts = plan.verdicts(pos[:, 0], (fl[:, 0] & N.AF_DONE) != 0, rew[:, 0])
     return emu, grid[0], pos0[0], verdict, counts, fields

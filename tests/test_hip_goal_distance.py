@@ -452,9 +452,11 @@ def _probe(name, prepare=None):
         fields[path] = fields[path][0]
     env.agent_state[:, 0] = torch.from_numpy(plan.records(rec[:, 0]).view(np.int64)).to(env.device)
     _, rew, _, _ = env.step(torch.from_numpy(plan.actions(env.num_agents)).to(env.device))
-    env.check_errors()
-    assert int(env.error_t.abs().sum()) == 0
     pos, _, fl = G.unpack_records(env.agent_state.cpu().numpy())
+    want_err = plan.errors(grid[0], env, pos[:, 0])     # (strict=False: the probes that leave a wall record what upstream raises)
+    assert np.array_equal(env.error_t.cpu().numpy(), want_err) and (want_err != 0).any() and (want_err == 0).any()
+    with pytest.raises(AssertionError):
+        env.check_errors()
     assert np.array_equal(pos[~plan.probed, 0], pos0[~plan.probed, 0])
     verdict, counts = plan.verdicts(pos[:, 0], (fl[:, 0] & N.AF_DONE) != 0, rew[:, 0].cpu().numpy())
     return env, grid[0], pos0[0], verdict, counts, fields

@@ -330,8 +330,9 @@ def test_atlas_of_every_object_kind_matches_the_oracle(ts):
             for k in range(n_ag):
                 for d in range(4):
                     assert np.array_equal(atlas[0, 1 + n_obj + (slot[i] * n_ag + k) * 4 + d], orc.tile(i, k, d)), (i, k, d)
-    # overlappable kinds: empty, Goal, open Door, Lava, Floor, BonusTile
-    assert n_slots == 6
+    # kinds that can hold agents: the overlappable ones — empty, Goal, open Door, Lava, Floor, BonusTile — and the closed Door
+    # (an open door shut on its occupant keeps it, objects.py:344-345; render_tile blends it over the door, base.py:288-294)
+    assert n_slots == 7 and slot[4] != 0xFF and slot[5] == 0xFF
 
 
 def test_object_registry_interface():

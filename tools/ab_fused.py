@@ -106,3 +106,4 @@ base = statistics.median(res[names[0]])
 for nm in names:
     m = statistics.median(res[nm])
     print("%s median %.4f ms (min %.4f max %.4f)  %+.2f%% vs %s" % (nm, m, min(res[nm]), max(res[nm]), 100 * (m / base - 1), names[0]))
+    print("%s series (ms, in the order run): %s" % (nm, " ".join("%.4f" % v for v in res[nm])))

@@ -29,6 +29,8 @@
  *                   store again the observation bands its output buffer already holds
  *   mg_goal_distance  (no reference counterpart: the exact number of left / right / forward actions from every agent, or every
  *                   state, to the step that enters a goal cell; -1 where there is no path)
+ *   mg_solve_distance (none either: the same through keys and doors — left / right / forward / pickup / toggle —, with the
+ *                   first action of a shortest path)
  *   mg_put_obj      MultiGridEnv.put_obj (base.py:655-662)
  *   mg_place        MultiGridEnv.place_obj / try_place_obj outside _gen_grid (base.py:664-708)
  *   mg_render_frame MultiGridEnv.render's whole-grid image: MultiGrid.render(top_agent=None) +
@@ -370,6 +372,41 @@ int32_t mg_goal_distance(const MgConfig* cfg, const MgState* st, const uint8_t* 
  * depend on it — mg_goal_distance is the call. */
 int32_t mg_goal_distance_path(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, int32_t* agent_dist,
                               int32_t* field, int32_t path, void* stream);
+
+/* Solve distance (no reference counterpart): mg_goal_distance's question with keys and doors in play.  For every selected env —
+ * env_mask as above — and every agent k of it: agent_dist[b][k] (device int32 [B][n_agents]) = the smallest number of actions
+ * out of `left` (0), `right` (1), `forward` (2), `pickup` (3) and `toggle` (5) after which agent k's `forward` ENTERS a goal
+ * cell — on the env's grid as it is now, the agent carrying what it carries now (MG_AG_CARRY), other agents ignored, under the
+ * step's own rules (base.py:530-613); -1: no such sequence, or the agent is in no cell, or it stands on a cell that is neither
+ * free nor a goal (a door shut on it included).  `drop` and `done` are never used, so an agent picks up at most ONE object:
+ * two locked doors of two colours in a row have no path.
+ *   Cells are mg_goal_distance's free / goal / blocked; nothing wraps, lava blocks, goals are entered and never crossed.  A
+ *   blocked cell becomes free in two ways.  An ITEM — a blocked cell whose object has MG_OF_CAN_PICKUP — is taken by `pickup`
+ *   with empty hands.  A SHUT DOOR — MG_OF_IS_DOOR without MG_OF_CAN_OVERLAP and MG_OF_IS_BOX — is opened by `toggle`: one
+ *   action if it is not locked (-> toggle_next), two if it is (-> unlock_next, a closed door, -> that door's toggle_next), the
+ *   second only for an agent that holds an MG_OF_IS_KEY object of the door's color_idx.  A door counts as openable only if the
+ *   id it ends as is a free cell; doors are never closed again; a box is never toggled.
+ *   Of each env the first max_doors (0 .. 4) shut doors and the first max_items (0 .. 3) items in grid index order x * H + y are
+ *   TRACKED; those beyond the caps block and are never touched.  env_exact[b] (device uint8 [B] or NULL) = 1 iff the env has
+ *   no more of either than the caps; where it is 0 every value is -1 or NOT SMALLER than the uncapped one.  For an agent that
+ *   already carries something no item is tracked (it cannot pick up).
+ * agent_action[b][k] (device int8 [B][n_agents] or NULL): the first action of such a path — the lowest action id whose
+ * successor state lies one action nearer (two for the first toggle of a locked door) —, 6 (`done`) where there is no path.
+ * After that action is stepped, the call on the new state gives exactly one less.  Rows of unselected envs are not written.
+ * One launch, one wave per selected env: mg_goal_distance's reverse search by levels over bit planes, in LDS, over the up to
+ * 2^D (1 + K) LAYERS (set of tracked doors opened, tracked item picked up or none) of the env's own D <= max_doors doors and
+ * K <= max_items items at once, the few edges between layers (pickup, open: cost 1; unlock and open: cost 2) taken per level
+ * from the states that face the object; once per class of carry among the env's agents.  LDS per env:
+ * 8 W ceil(H / 64) (2 + 12 (1 + max_items) 2^max_doors) + 1024 bytes (mg_solve_distance_lds_bytes) — 18.1 KiB at 15 x 15 with
+ * (2, 2); 255 x 255 fits with (0, 0) only.
+ * Only B, W, H, n_agents, cells_stride, n_obj and obj of cfg are read (1 <= W, H <= 255), and grid and agents of st.
+ * MG_E_ARG: a NULL cfg, st, agent_dist, grid, agents or obj, a size outside those bounds, max_doors outside 0 .. 4 or max_items
+ * outside 0 .. 3; MG_E_UNSUPPORTED: the layers need more than 160 KiB of LDS — worked out on the host: nothing is launched,
+ * nothing written. */
+int32_t mg_solve_distance(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, int32_t max_doors, int32_t max_items,
+                          int32_t* agent_dist, int8_t* agent_action, uint8_t* env_exact, void* stream);
+/* the LDS bytes per env mg_solve_distance needs for the shape and the caps (it runs iff they are <= 160 KiB); MG_E_ARG as above */
+int32_t mg_solve_distance_lds_bytes(int32_t W, int32_t H, int32_t max_doors, int32_t max_items);
 
 /* actions: device [B][n_agents], element size `action_bytes` in {1,4,8} (little-endian ints).
  * rewards: device float32 [B][n_agents].  Sets st->done[b].

@@ -109,6 +109,7 @@ class PlaceStats(C.Structure):
 
 LEVEL_PUBLISH, LEVEL_PENDING, LEVEL_MASK = 0, 1, 2      # MG_LEVEL_* (mg_level_apply's rule)
 GOAL_PATH_AUTO, GOAL_PATH_REG, GOAL_PATH_LDS = 0, 1, 2  # mg_goal_distance_path's path
+SOLVE_MAX_DOORS, SOLVE_MAX_ITEMS, SOLVE_LDS_LIMIT = 4, 3, 160 * 1024   # mg_solve_distance's caps and the LDS it may ask for
 
 DELTA_FORCE = 1            # MG_DELTA_FORCE (mg_step_render_delta)
 
@@ -146,7 +147,8 @@ SYMBOLS = ["mg_abi_version", "mg_struct_sizes", "mg_host_flag_alloc", "mg_host_f
            "mg_spec_info_struct_size", "mg_render_specialize", "mg_step_render_spec", "mg_render_obs_spec",
            "mg_render_spec_release", "mg_rtc_source",
            "mg_level_seed", "mg_level_apply", "mg_level_apply_rows",
-           "mg_goal_distance", "mg_goal_distance_path"]
+           "mg_goal_distance", "mg_goal_distance_path",
+           "mg_solve_distance", "mg_solve_distance_lds_bytes"]
 
 _lib = None
 _path = LIB_PATH
@@ -220,6 +222,9 @@ def lib():
     # (cfg, st, env_mask, agent_dist, field, stream) / (..., field, path, stream)
     L.mg_goal_distance.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp, vp, vp]
     L.mg_goal_distance_path.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp, vp, i32, vp]
+    # (cfg, st, env_mask, max_doors, max_items, agent_dist, agent_action, env_exact, stream) / (W, H, max_doors, max_items)
+    L.mg_solve_distance.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, i32, vp, vp, vp, vp]
+    L.mg_solve_distance_lds_bytes.argtypes = [i32, i32, i32, i32]
     L.mg_reset.argtypes = [C.POINTER(Config), C.POINTER(State), C.POINTER(GenProgram), vp, vp]
     L.mg_step.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp]
     L.mg_step_render.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp]

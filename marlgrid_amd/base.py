@@ -1074,10 +1074,44 @@ class MultiGridEnv(object):
         return self._goal.distance(env_mask, env_ids, field, _path)
 
     @_on_device
+    def solve_distance(self, env_mask=None, env_ids=None, max_doors=2, max_items=2, policy=False):
+        """`goal_distance` with keys and doors in play: the exact number of actions out of `left` (0), `right` (1), `forward` (2),
+        `pickup` (3) and `toggle` (5) after which each agent's `forward` ENTERS a goal cell — on its env's grid as it is now, the
+        agent carrying what it carries now, other agents ignored, under step()'s own rules.  The env-owned (B, n) int32 tensor,
+        -1 where no such sequence exists, the agent is in no cell, or it stands on a cell that is neither free nor a goal (a door
+        shut on it included).  With `policy=True` the pair (dist, action): action (B, n) int64, ready for `env.step`, is the
+        first action of such a path — the lowest action id that leads one action nearer (a locked door's first toggle: two) —
+        and 6 (`done`) where there is no path; after stepping it, a fresh call gives exactly one less.  Selectors and tensors
+        behave as `goal_distance`'s: updated for the selected envs only, -1 / 6 at the start, made at the first call.
+
+        `drop` and `done` are never used, so an agent picks up at most ONE object: two locked doors of two colours in a row
+        have no path — that is part of the definition.  A closed door costs one toggle, a locked one two (unlock, open) by an
+        agent holding a key of its colour; a door counts only if it ends as a cell that can be walked on, and is never closed
+        again; a box is never toggled; pickup empties the cell of anything that can be picked up.  Everything else is
+        `goal_distance`'s: nothing wraps, lava blocks, goals are entered and never crossed.
+
+        Per env the first `max_doors` (0 .. 4) shut doors and the first `max_items` (0 .. 3) items in grid order are tracked;
+        those beyond block and are never touched, and an agent that already carries something tracks no item.
+        `env.solve_exact` — (B,) bool, of the last call's envs — says where nothing was beyond the caps; elsewhere every value is
+        -1 or not smaller than the uncapped one.  The search keeps 2^max_doors * (1 + max_items) layers in LDS; caps that do not
+        fit for the grid's size raise NotImplementedError, naming the bytes and the caps that would fit, before anything is
+        launched.
+
+        One launch on the current stream (mg_solve_distance: a wave per selected env), nothing is read back; an env that never
+        calls it allocates and launches nothing.  Derived values: no part of state_dict()."""
+        return self._goal.solve(env_mask, env_ids, max_doors, max_items, policy)
+
+    @property
+    def solve_exact(self):
+        """(B,) bool: where the last `solve_distance` call tracked every shut door and item (None before the first call)"""
+        return self._goal.exact
+
+    @_on_device
     def optimal_return(self, dist=None):
         """(B, n) float64: what an agent that takes a shortest path from here earns — R * (1 - 0.9 * (step_count + d) /
         max_steps), R without reward_decay, and 0 where d < 0 (no path) or step_count + d > max_steps (the episode is truncated
-        first).  `dist`: a (B, n) tensor of distances, default `goal_distance()` of every env now.  R is the reward the
+        first).  `dist`: a (B, n) tensor of distances, default `goal_distance()` of every env now; `solve_distance()`'s tensor gives
+        the return of a shortest path through keys and doors.  R is the reward the
         registered Goal kinds share (ValueError if they differ or there is none).  Torch ops only."""
         return self._goal.optimal_return(dist)
 

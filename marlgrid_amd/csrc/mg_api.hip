@@ -5,6 +5,7 @@
 
 #include "mg_device.h"
 #include "mg_launch.h"
+#include "mg_solve_core.h"
 
 namespace {
 
@@ -205,6 +206,24 @@ int32_t mg_goal_distance_path(const MgConfig* cfg, const MgState* st, const uint
 int32_t mg_goal_distance(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, int32_t* agent_dist, int32_t* field,
                          void* stream) {
     return mg_goal_distance_path(cfg, st, env_mask, agent_dist, field, 0, stream);
+}
+
+int32_t mg_solve_distance(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, int32_t max_doors, int32_t max_items,
+                          int32_t* agent_dist, int8_t* agent_action, uint8_t* env_exact, void* stream) {
+    if (!cfg || !st || !agent_dist || !st->grid || !st->agents || !cfg->obj) return MG_E_ARG;
+    if (cfg->B < 0 || cfg->W < 1 || cfg->H < 1 || cfg->W > 255 || cfg->H > 255 || cfg->n_agents < 1 || cfg->n_agents > MG_MAX_AGENTS)
+        return MG_E_ARG;
+    if (cfg->cells_stride < cfg->W * cfg->H || cfg->n_obj < 1 || cfg->n_obj > MG_MAX_OBJ) return MG_E_ARG;
+    if (max_doors < 0 || max_doors > 4 || max_items < 0 || max_items > 3) return MG_E_ARG;
+    int unsupported = 0;
+    const hipError_t e = mg::launch_solve_distance(*cfg, *st, env_mask, max_doors, max_items, agent_dist, agent_action, env_exact,
+                                                   (hipStream_t)stream, &unsupported);
+    return unsupported ? MG_E_UNSUPPORTED : rc(e);
+}
+
+int32_t mg_solve_distance_lds_bytes(int32_t W, int32_t H, int32_t max_doors, int32_t max_items) {
+    if (W < 1 || H < 1 || W > 255 || H > 255 || max_doors < 0 || max_doors > 4 || max_items < 0 || max_items > 3) return MG_E_ARG;
+    return (int32_t)mg::solve_scratch_bytes(W, H, max_doors, max_items);
 }
 
 int32_t mg_episode_struct_size(void) { return (int32_t)sizeof(MgEpisode); }

@@ -51,4 +51,7 @@ hipError_t launch_level_apply_rows(const MgConfig& cfg, const MgState& st, int r
 // force either; *unsupported = 1 and nothing launched when the forced or the only path cannot take the shape
 hipError_t launch_goal_distance(const MgConfig& cfg, const MgState& st, const uint8_t* mask, int32_t* agent_dist, int32_t* field,
                                 int path, hipStream_t s, int* unsupported);
+// solve distance (mg_solve_dist.hip): *unsupported = 1 and nothing launched when the layers of (max_doors, max_items) do not fit LDS
+hipError_t launch_solve_distance(const MgConfig& cfg, const MgState& st, const uint8_t* mask, int max_doors, int max_items,
+                                 int32_t* agent_dist, int8_t* agent_action, uint8_t* env_exact, hipStream_t s, int* unsupported);
 }  // namespace mg

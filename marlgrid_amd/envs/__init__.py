@@ -13,7 +13,9 @@ then recorded once per path and every env runs the ops of its own path (`Colored
 colours).  `self._param(name, lo, hi)` is used like a draw but read per env from `env.params[name]` (`env.set_params`) at every
 reset: `ClutteredMultiGrid(n_clutter_max=K)` scatters `count=self._param("n_clutter", 0, K + 1)` blocks.  `_gen_grid` still
 cannot put a draw or a parameter into `agent_spawn_kwargs` or have a `reject_fn` that depends on one.  Upstream registers
-no DoorKey id; the ids in `extension_envs` are this package's own and are built by `make` like the registered ones.
+no DoorKey id; the ids in `extension_envs` are this package's own and are built by `make` like the registered ones, and so
+are the one-agent DoorKey ids in `solo_envs` (`env.solve_distance(policy=True)` is followed by an agent that has its level
+to itself).
 """
 import functools
 import random
@@ -27,6 +29,9 @@ _PALETTE = ("red", "blue", "purple", "orange", "olive", "pink")     # per-slot a
 _registry = {}            # id -> factory(**constructor kwargs)
 registered_envs = []      # ids, in registration order (upstream's list of the same name)
 extension_envs = []       # ids upstream does not register (DoorKey): `make` builds them, `registered_envs` stays upstream's list
+solo_envs = []            # ... and their one-agent forms (following `solve_distance`'s policy needs the level to oneself): `make` builds
+_solo_registry = {}       # them too, from a table of their own — `_registry` and `extension_envs` are the ids whose recordings and
+                          # launch tables are pinned one by one
 
 
 def _construct(env_class, n_agents, geometry, agent_color, fixed, **extra):
@@ -63,9 +68,9 @@ def make(env_name, pipeline=None, devices=None, **kwargs):
     a device named m > 1 times gives its shards `share=m` in `place_obs`.  Not together with `pipeline`, `seeds` or
     `device`."""
     try:
-        factory = _registry[env_name]
+        factory = _registry[env_name] if env_name in _registry else _solo_registry[env_name]
     except KeyError:
-        raise KeyError("unknown env id %r; registered: %s" % (env_name, ", ".join(registered_envs + extension_envs))) from None
+        raise KeyError("unknown env id %r; registered: %s" % (env_name, ", ".join(registered_envs + extension_envs + solo_envs))) from None
     if devices is not None:
         from ..sharding import DeviceShards, merge_share
         if pipeline is not None:
@@ -126,6 +131,9 @@ for _row in (("MarlGrid-2AgentDoorKey6x6-v0", 6), ("MarlGrid-2AgentDoorKey8x8-v0
     register_marl_env(_row[0], DoorKeyEnv, n_agents=2, grid_size=_row[1], view_size=7, listed_in=extension_envs)
 register_marl_env("MarlGrid-2AgentColoredDoorKey8x8-v0", ColoredDoorKeyEnv, n_agents=2, grid_size=8, view_size=7,
                   listed_in=extension_envs)
+for _row in (("MarlGrid-1AgentDoorKey6x6-v0", 6), ("MarlGrid-1AgentDoorKey8x8-v0", 8)):
+    _solo_registry[_row[0]] = functools.partial(_construct, DoorKeyEnv, 1, (7, 0), None, dict(grid_size=_row[1]))
+    solo_envs.append(_row[0])
 # a curriculum over the clutter: every env reads its number of wall blocks, 0 .. 50, from `env.params["n_clutter"]` when it resets
 register_marl_env("MarlGrid-3AgentClutteredCurriculum15x15-v0", ClutteredMultiGrid, n_agents=3, grid_size=15, view_size=7,
                   env_kwargs=dict(n_clutter=25, n_clutter_max=50), listed_in=extension_envs)

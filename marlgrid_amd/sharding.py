@@ -319,6 +319,21 @@ class _Shards(object):
         none = {"env_ids": np.zeros(0, np.int64)}
         return self._each(lambda k, env: env.goal_distance(field=field, **(none if parts[k] is None else parts[k])))
 
+    def solve_distance(self, env_mask=None, env_ids=None, max_doors=2, max_items=2, policy=False):
+        """`MultiGridEnv.solve_distance` for the whole batch: `env_mask` / `env_ids` in GLOBAL env order, split by `ranges`; every
+        shard launches on its own stream.  Per shard: its env's (rows, n) tensor, or with `policy=True` its (dist, action) pair
+        (a shard none of `env_ids` falls into selects nothing and returns its tensors as they are)."""
+        import numpy as np
+        parts = split_params(self.ranges, env_mask=env_mask, env_ids=env_ids, _who="solve_distance")
+        none = {"env_ids": np.zeros(0, np.int64)}
+        return self._each(lambda k, env: env.solve_distance(max_doors=max_doors, max_items=max_items, policy=policy,
+                                                            **(none if parts[k] is None else parts[k])))
+
+    @property
+    def solve_exact(self):
+        """per shard: its env's `solve_exact`"""
+        return [env.solve_exact for env in self.envs]
+
     @property
     def params(self):
         """per shard: its env's `params` (name -> the shard's (rows,) uint8 column)"""

@@ -31,6 +31,8 @@
  *                   state, to the step that enters a goal cell; -1 where there is no path)
  *   mg_solve_distance (none either: the same through keys and doors — left / right / forward / pickup / toggle —, with the
  *                   first action of a shortest path)
+ *   mg_fork_rows / mg_rollout  (none either: rows of the batch copied into a shadow state and stepped T times there — what T
+ *                   MultiGridEnv.step calls WOULD return, the env untouched)
  *   mg_put_obj      MultiGridEnv.put_obj (base.py:655-662)
  *   mg_place        MultiGridEnv.place_obj / try_place_obj outside _gen_grid (base.py:664-708)
  *   mg_render_frame MultiGridEnv.render's whole-grid image: MultiGrid.render(top_agent=None) +
@@ -407,6 +409,36 @@ int32_t mg_solve_distance(const MgConfig* cfg, const MgState* st, const uint8_t*
                           int32_t* agent_dist, int8_t* agent_action, uint8_t* env_exact, void* stream);
 /* the LDS bytes per env mg_solve_distance needs for the shape and the caps (it runs iff they are <= 160 KiB); MG_E_ARG as above */
 int32_t mg_solve_distance_lds_bytes(int32_t W, int32_t H, int32_t max_doors, int32_t max_items);
+
+/* Lookahead (no reference counterpart): "what happens if these agents do THIS for the next T steps", asked of the simulator
+ * without doing it.  A second, SHADOW MgState — caller-owned, R rows, its error_flag NULL — is filled with copies of env rows
+ * (mg_fork_rows) and stepped through one plan of T actions per row in one launch (mg_rollout); the env's state is only read.
+ *
+ * mg_fork_rows: for r in [0, R), row d = dst_of_row[r] (device int64 [R]; NULL: d = r) of `dst` becomes a copy of row
+ * s = src_of_dst[r % m] (device int64 [m]; NULL: s = r % m) of `src`: grid slice, agent records, generator (mt, mt_pos, mt_head),
+ * step_count, done, error, and prestige when cfg->prestige_mask != 0.  cfg->B is the number of rows of `src`; only B, n_agents,
+ * cells_stride and prestige_mask of cfg are read.  s outside [0, cfg->B): the row is made INERT — an ended episode (every
+ * record MG_AF_DONE, step_count INT32_MAX, done 1, error 0, grid and generator zero) that mg_rollout never steps.  d outside
+ * [0, dst_B): nothing is written for r.  Two r naming one d are the caller's error; `src` and `dst` must not overlap.
+ * One wave per row, 16-byte vectors for the 2 496-byte generator, its head and the grid slice (bytes where a slice is not
+ * 16-byte aligned); the R / m rows that read one source row are neighbours in the launch.  m >= 1 and R a multiple of m.
+ * MG_E_ARG: a NULL cfg or state array, mt / mt_head of either state not 16-byte aligned, R, m or dst_B out of range. */
+int32_t mg_fork_rows(const MgConfig* cfg, const MgState* src, const MgState* dst, const int64_t* src_of_dst,
+                     const int64_t* dst_of_row, int32_t dst_B, int32_t R, int32_t m, void* stream);
+/* mg_rollout: every row r of the shadow state `st` (cfg->B = R rows, plan-major: r = p * m + j — plan p of env j —, K = R / m
+ * plans) is stepped T times as mg_step with auto_reset == NULL would step it, step t with actions[p][t][j][.]:
+ *   actions  device [K][T][m][n_agents], element size `action_bytes` in {1, 4, 8}
+ *   rewards  device float32 [K][T][m][n_agents];  done: device uint8 [K][T][m]
+ *   errors   device int32 [R] or NULL: the first MG_ERR_* a step of the row recorded in this call, 0 for none (st->error[r] is
+ *            cleared when the call begins: what the copied env had recorded is the env's)
+ * with one difference: a rollout STOPS AT ITS EPISODE'S END.  "Ended" is read off the row's state before each step — step_count >=
+ * max_steps, or every record MG_AF_DONE: what next-step reset reads, never st->done —; from then on the row is frozen, its
+ * rewards are 0 and done is 1.  A row whose episode had ended when it was copied, and an inert row, are frozen from t = 0.
+ * Nothing resets, no reset program is read, st->error_flag should be NULL.  One launch, one lane per row, the bodies mg_step
+ * runs (so the rewards are bit-identical to T mg_step calls); results are independent of K and of the other rows.
+ * MG_E_ARG: what mg_step answers it for, a NULL done, T < 0, m < 1, or cfg->B no multiple of m. */
+int32_t mg_rollout(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, int32_t T, int32_t m,
+                   float* rewards, uint8_t* done, int32_t* errors, void* stream);
 
 /* actions: device [B][n_agents], element size `action_bytes` in {1,4,8} (little-endian ints).
  * rewards: device float32 [B][n_agents].  Sets st->done[b].

@@ -148,7 +148,8 @@ SYMBOLS = ["mg_abi_version", "mg_struct_sizes", "mg_host_flag_alloc", "mg_host_f
            "mg_render_spec_release", "mg_rtc_source",
            "mg_level_seed", "mg_level_apply", "mg_level_apply_rows",
            "mg_goal_distance", "mg_goal_distance_path",
-           "mg_solve_distance", "mg_solve_distance_lds_bytes"]
+           "mg_solve_distance", "mg_solve_distance_lds_bytes",
+           "mg_fork_rows", "mg_rollout"]
 
 _lib = None
 _path = LIB_PATH
@@ -225,6 +226,9 @@ def lib():
     # (cfg, st, env_mask, max_doors, max_items, agent_dist, agent_action, env_exact, stream) / (W, H, max_doors, max_items)
     L.mg_solve_distance.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, i32, vp, vp, vp, vp]
     L.mg_solve_distance_lds_bytes.argtypes = [i32, i32, i32, i32]
+    # (cfg, src, dst, src_of_dst, dst_of_row, dst_B, R, m, stream) / (cfg, st, actions, action_bytes, T, m, rewards, done, errors, stream)
+    L.mg_fork_rows.argtypes = [C.POINTER(Config), C.POINTER(State), C.POINTER(State), vp, vp, i32, i32, i32, vp]
+    L.mg_rollout.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, i32, i32, vp, vp, vp, vp]
     L.mg_reset.argtypes = [C.POINTER(Config), C.POINTER(State), C.POINTER(GenProgram), vp, vp]
     L.mg_step.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp]
     L.mg_step_render.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp]

@@ -38,6 +38,7 @@ from .agents import GridAgentInterface
 from .gen_edits import EditTable
 from .gen_params import ParamTable
 from .goal import EnvGoal
+from .lookahead import EnvLookahead
 from .gen_recorder import GenDraw, GenRecorder, _NO_BRANCH, _any_draw, _gen_add, _trace, decode_program, pack_program
 from .levels import EnvLevels, LevelBank
 from . import launch_tables as LT
@@ -535,6 +536,7 @@ class MultiGridEnv(object):
         self._params = ParamTable(self)     # the per-env parameters of `_gen_grid` (gen_params.py)
         self._levels = EnvLevels(self)      # replayable levels (levels.py): nothing is allocated or launched until set_levels
         self._goal = EnvGoal(self)          # goal distance (goal.py): nothing is allocated or launched until goal_distance
+        self._look = EnvLookahead(self)     # lookahead (lookahead.py): nothing is allocated or launched until lookahead / fork
         # level_edits=K (0..64): every env holds a list of K cell edits (x, y, kind, on) that its every reset applies behind
         # what `_gen_grid` laid out and before the agents are placed (an EDITS op at the end of the reset program; set_edits).
         # 0: no table, no op — recordings, programs and launches are what they were
@@ -1114,6 +1116,53 @@ class MultiGridEnv(object):
         the return of a shortest path through keys and doors.  R is the reward the
         registered Goal kinds share (ValueError if they differ or there is none).  Torch ops only."""
         return self._goal.optimal_return(dist)
+
+    # ---- lookahead: what T steps WOULD return, on a shadow copy of the state --------------------------------------------------
+    @_on_device
+    def lookahead(self, actions, env_ids=None):
+        """What `T` successive `step()` calls of an `auto_reset=False` env in this env's present state would return for each of
+        K action plans — without doing them.  `actions`: an integer tensor (K, T, m, n) or (T, m, n) (K = 1) on the env's device,
+        of any dtype step() takes; m = len(env_ids), or B without `env_ids`; plan p of env j is `actions[p, :, j, :]`.  Returns
+        the env-owned pair (rewards (K, T, m, n) float32, done (K, T, m) bool), rewritten by the next call of the same shape.
+        `env_ids`: host ids are checked (ValueError); of a device tensor nothing is read back, and an id outside the batch makes
+        that row inert — frozen, reward 0, done True.
+
+        Every plan starts from a copy of the env's state, generator included: the shuffle orders are the ones the env itself
+        would draw next, and the rewards are bit-identical to step()'s.  One difference: a rollout STOPS AT ITS EPISODE'S END —
+        from the first step that reports `done` on, the row is frozen, its rewards are 0 and `done` stays True; an env whose
+        episode has already ended (auto_reset="next_step": the terminal state) is frozen from the first row.  Nothing resets
+        inside a lookahead: no reset program, level or parameter is read.
+
+        The env is untouched: no byte of its state, error array, host error flag, observation buffers or episode accumulators
+        changes.  Errors a simulated step records go to `env.lookahead_errors`, and `strict` never raises for a plan.
+
+        Two launches on the current stream (mg_fork_rows: a wave per shadow row; mg_rollout: a lane per shadow row, all T steps),
+        nothing is read back, no host synchronisation.  The shadow state — K * m rows of cells_stride + 8 n + 2 573 bytes — is
+        made at the first call and re-made only when K * m grows.  Out of scope: observations of simulated states, lookahead
+        through a reset, plans whose shuffles differ."""
+        return self._look.lookahead(actions, env_ids)
+
+    @property
+    def lookahead_errors(self):
+        """(K, m) int32 of the last `lookahead` call: the first error code (MG_ERR_*: 1 ValueError — an action outside 0..6 —, 2
+        RecursionError, ...) a simulated step of the row recorded, 0 for none; None before the first call"""
+        return self._look.errors
+
+    @_on_device
+    def fork(self, src_ids, dst_ids):
+        """Branch the batch: env `dst_ids[i]` becomes a copy of env `src_ids[i]` — everything state_dict() carries: grid, agent
+        records, generator and head, step count, done, error, 'prestige', the episode_info accumulators, the env's parameter and
+        edit rows, and with set_levels the running level and the slot it resets to.  The copy goes through staging rows (gather,
+        then scatter: two launches), so a row may be a source and a destination of one call.  Host ids are checked — a `dst`
+        named twice is a ValueError —; of device tensors nothing is read back: a `dst` named twice is the caller's error, and a
+        pair with an id outside the batch copies nothing.  With `set_levels(seeds=)` the env's own bank row — seed and
+        generator — is copied, so `dst` can be re-seeded by its own id afterwards and re-seeding `src` leaves it alone; with a
+        caller's bank `dst` takes `src`'s slot.
+
+        Two copies given the same actions stay byte-identical for ever: they hold the same generator.  The observation tensors
+        last returned are stale for the `dst` rows until `gen_obs()` or the next `step()`; the call ends with `invalidate_obs()`,
+        so an obs_delta step redraws them."""
+        self._look.fork(src_ids, dst_ids)
 
     # ---- branching on a draw: one recorded run of `_gen_grid` per path, merged into one guarded program --------------
     def _fork(self, d):

@@ -226,6 +226,30 @@ int32_t mg_solve_distance_lds_bytes(int32_t W, int32_t H, int32_t max_doors, int
     return (int32_t)mg::solve_scratch_bytes(W, H, max_doors, max_items);
 }
 
+int32_t mg_fork_rows(const MgConfig* cfg, const MgState* src, const MgState* dst, const int64_t* src_of_dst, const int64_t* dst_of_row,
+                     int32_t dst_B, int32_t R, int32_t m, void* stream) {
+    if (!cfg || cfg->B < 0 || cfg->n_agents < 1 || cfg->n_agents > MG_MAX_AGENTS || cfg->cells_stride < 1) return MG_E_ARG;
+    int e = check_state(src);
+    if (e) return e;
+    e = check_state(dst);
+    if (e) return e;
+    if (cfg->prestige_mask && (!src->prestige || !dst->prestige)) return MG_E_ARG;
+    if (R < 0 || dst_B < 0 || m < 1 || R % m != 0) return MG_E_ARG;
+    // (generator rows are 2 496 and 64 bytes, copied as 16-byte vectors: aligned bases keep every row aligned)
+    if ((reinterpret_cast<uintptr_t>(src->mt) | reinterpret_cast<uintptr_t>(src->mt_head) | reinterpret_cast<uintptr_t>(dst->mt) |
+         reinterpret_cast<uintptr_t>(dst->mt_head)) & 15)
+        return MG_E_ARG;
+    return rc(mg::launch_fork_rows(*cfg, *src, *dst, src_of_dst, dst_of_row, dst_B, R, m, (hipStream_t)stream));
+}
+
+int32_t mg_rollout(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, int32_t T, int32_t m,
+                   float* rewards, uint8_t* done, int32_t* errors, void* stream) {
+    const int e = check_step_args(cfg, st, actions, action_bytes, rewards, nullptr, nullptr, false);
+    if (e) return e;
+    if (!done || T < 0 || m < 1 || cfg->B % m != 0) return MG_E_ARG;
+    return rc(mg::launch_rollout(*cfg, *st, actions, action_bytes, T, m, rewards, done, errors, (hipStream_t)stream));
+}
+
 int32_t mg_episode_struct_size(void) { return (int32_t)sizeof(MgEpisode); }
 
 int32_t mg_step_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,

@@ -54,4 +54,9 @@ hipError_t launch_goal_distance(const MgConfig& cfg, const MgState& st, const ui
 // solve distance (mg_solve_dist.hip): *unsupported = 1 and nothing launched when the layers of (max_doors, max_items) do not fit LDS
 hipError_t launch_solve_distance(const MgConfig& cfg, const MgState& st, const uint8_t* mask, int max_doors, int max_items,
                                  int32_t* agent_dist, int8_t* agent_action, uint8_t* env_exact, hipStream_t s, int* unsupported);
+// lookahead (mg_lookahead.hip): rows of one state copied into another (one wave per row), and a shadow state's rows stepped T times
+hipError_t launch_fork_rows(const MgConfig& cfg, const MgState& src, const MgState& dst, const int64_t* src_of_dst,
+                            const int64_t* dst_of_row, int dst_B, int R, int m, hipStream_t s);
+hipError_t launch_rollout(const MgConfig& cfg, const MgState& st, const void* actions, int action_bytes, int T, int m, float* rewards,
+                          uint8_t* done, int32_t* errors, hipStream_t s);
 }  // namespace mg

@@ -172,6 +172,23 @@ class LevelBank(object):
                 for r in others:
                     r.wait_event(ev)
 
+    def copy_rows(self, put):
+        """`put(tensor)` for each of this bank's row tensors — seeds, generators, and a full bank's rows — on torch's current
+        stream, ordered against the streams that read the bank as `_seed_rows` is (MultiGridEnv.fork, the seeds form)"""
+        import torch
+        with torch.cuda.device(self.device):
+            cur = torch.cuda.current_stream(self.device)
+            others = [r for r in self._readers.values() if r != cur]
+            for r in others:
+                cur.wait_event(r.record_event())
+            for t in (self.seeds, self.mt, self.pos, self.head, self.params, self.edits):
+                if t is not None:
+                    put(t)
+            if others:
+                ev = cur.record_event()
+                for r in others:
+                    r.wait_event(ev)
+
     def replica(self, device, streams=()):
         """this bank's levels on `device`, for shards that live there and step on `streams`: seeded there from `seeds` (one
         launch, no generator crosses devices) and kept up to date by `assign`"""
@@ -281,6 +298,21 @@ class EnvLevels(object):
         else:
             N.check(env._lib.mg_level_apply(*head, stream))
         self.launches += 1
+
+    def fork(self, put):
+        """MultiGridEnv.fork: the `dst` envs take the running level and the NEXT level of their `src` envs — `put(tensor)`
+        copies rows src -> dst of a (B, ...) tensor.  With a caller's bank the next level is a slot, and the slot is copied.  In
+        the seeds form row b of the env's own bank is env b's and `level_of_env` stays `arange(B)`: the bank ROW is copied —
+        seed and generator —, so that a later `set_levels(seeds=, env_ids=[dst])` still reaches the env it names, and
+        re-seeding `src` leaves `dst` alone."""
+        if not self.on:
+            return
+        put(self.env.episode_level)
+        if self.bank is not None and self.bank is self.own_bank:
+            self.bank._readers.update(self.env._launch_streams)
+            self.bank.copy_rows(put)
+        else:
+            put(self.level_of_env)
 
     def next(self):
         """(B,) int64: the seed each env's next reset will use, resolved through the bank (-1: free-running)"""

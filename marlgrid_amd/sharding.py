@@ -138,6 +138,12 @@ def split_params(ranges, env_mask=None, env_ids=None, _who="set_params", **value
     return out
 
 
+def _host_ids(env_ids, B, who):
+    """global env ids on the host, range-checked (a device tensor is copied: a host sync)"""
+    from . import per_env as P
+    return P.host_ids(env_ids, B, who, any_number=True)
+
+
 def split_levels(ranges, ids=None, seeds=None, env_mask=None, env_ids=None):
     """`MultiGridEnv.set_levels` arguments in GLOBAL env order -> one dict of keyword arguments per (lo, hi) of `ranges` (None for
     a shard that none of `env_ids` falls into), as `split_params` splits a parameter: exactly one of `ids` (bank slots) and
@@ -328,6 +334,54 @@ class _Shards(object):
         none = {"env_ids": np.zeros(0, np.int64)}
         return self._each(lambda k, env: env.solve_distance(max_doors=max_doors, max_items=max_items, policy=policy,
                                                             **(none if parts[k] is None else parts[k])))
+
+    def lookahead(self, actions, env_ids=None):
+        """`MultiGridEnv.lookahead` for the whole batch: `actions` (K, T, m, n) or (T, m, n) and `env_ids` in GLOBAL env order,
+        split by `ranges` — the env axis of `actions` with them —; every shard launches on its own stream.  Per shard: its env's
+        (rewards, done) pair for the envs of the selection that are its own, in the selection's order (a shard none of
+        `env_ids` falls into returns empty tensors)."""
+        import numpy as np
+        import torch
+        if not torch.is_tensor(actions):
+            actions = torch.as_tensor(np.asarray(actions))
+        if actions.dim() == 3:
+            actions = actions.unsqueeze(0)
+        B = self.ranges[-1][1]
+        ids = None if env_ids is None else _host_ids(env_ids, B, "lookahead")
+        if actions.dim() != 4 or actions.shape[2] != (B if ids is None else len(ids)):
+            raise ValueError("lookahead: actions must have shape (K, T, %d, n), got %s"
+                             % (B if ids is None else len(ids), tuple(actions.shape)))
+
+        def one(k, env):
+            lo, hi = self.ranges[k]
+            if ids is None:
+                return env.lookahead(actions[:, :, lo:hi])
+            sel = np.nonzero((ids >= lo) & (ids < hi))[0]
+            return env.lookahead(actions[:, :, sel.tolist()], env_ids=ids[sel] - lo)
+        return self._each(one)
+
+    @property
+    def lookahead_errors(self):
+        """per shard: its env's `lookahead_errors`"""
+        return [env.lookahead_errors for env in self.envs]
+
+    def fork(self, src_ids, dst_ids):
+        """`MultiGridEnv.fork` with ids in GLOBAL env order (read on the host).  A copy stays within one shard: a pair of ids that
+        crosses shards raises NotImplementedError, before anything is copied."""
+        import numpy as np
+        B = self.ranges[-1][1]
+        src, dst = _host_ids(src_ids, B, "fork(src_ids=)"), _host_ids(dst_ids, B, "fork(dst_ids=)")
+        if src.size != dst.size:
+            raise ValueError("fork: %d src_ids for %d dst_ids" % (src.size, dst.size))
+        if len(set(dst.tolist())) != dst.size:
+            raise ValueError("fork: a dst env is named twice (%s)" % dst.tolist())
+        los = np.asarray([lo for lo, _ in self.ranges])
+        ks, kd = np.searchsorted(los, src, side="right") - 1, np.searchsorted(los, dst, side="right") - 1
+        if (ks != kd).any():
+            i = int(np.nonzero(ks != kd)[0][0])
+            raise NotImplementedError("fork: env %d is on shard %d and env %d on shard %d; a copy stays within one shard"
+                                      % (src[i], ks[i], dst[i], kd[i]))
+        self._each(lambda k, env: env.fork(src[ks == k] - los[k], dst[kd == k] - los[k]) if (ks == k).any() else None)
 
     @property
     def solve_exact(self):

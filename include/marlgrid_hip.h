@@ -33,6 +33,8 @@
  *                   first action of a shortest path)
  *   mg_fork_rows / mg_rollout  (none either: rows of the batch copied into a shadow state and stepped T times there — what T
  *                   MultiGridEnv.step calls WOULD return, the env untouched)
+ *   mg_explore_update  (none either: per agent, the world cells its observations have covered this episode and how often it
+ *                   stood on each cell — what count-based exploration bonuses are made of)
  *   mg_put_obj      MultiGridEnv.put_obj (base.py:655-662)
  *   mg_place        MultiGridEnv.place_obj / try_place_obj outside _gen_grid (base.py:664-708)
  *   mg_render_frame MultiGridEnv.render's whole-grid image: MultiGrid.render(top_agent=None) +
@@ -439,6 +441,28 @@ int32_t mg_fork_rows(const MgConfig* cfg, const MgState* src, const MgState* dst
  * MG_E_ARG: what mg_step answers it for, a NULL done, T < 0, m < 1, or cfg->B no multiple of m. */
 int32_t mg_rollout(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, int32_t T, int32_t m,
                    float* rewards, uint8_t* done, int32_t* errors, void* stream);
+
+/* Exploration maps (no reference counterpart).  Per env b and agent k, caller-owned device memory, kept up to date by ONE call
+ * after every mg_reset (with the reset's mask) and after every step launch (mask NULL), i.e. once per observation returned:
+ *   seen         uint8 [B][n_agents][W][H], index [b][k][x][y]: 1 iff cell (x, y) was inside agent k's view AND VISIBLE in at
+ *                least one observation since the env's running episode began
+ *   visits       int32 [B][n_agents][W][H]: the number of those observations in which agent k was placed (MG_AF_PLACED) on (x, y)
+ *   new_cells    int32 [B][n_agents]: how many cells this call added to seen[b][k]
+ *   visit_count  int32 [B][n_agents]: visits[b][k] at agent k's own cell after this call's increment; 0 for an agent in no cell
+ * VISIBLE is exactly the vis_mask of the reference's gen_obs_grid(agent) (base.py:418-451): crop at get_view_exts, rotate dir + 1
+ * times, process_vis — all ones with see_through_walls, all zeros for a viewer that is not MG_AF_ACTIVE (base.py:420-425),
+ * clipped to the grid, the transparency that of the grid's own object (base.py:103-106); hide_item_types plays no part.  It is
+ * taken on the state `st` holds, which is the state the returned observation shows.
+ * A FRESH EPISODE CLEARS FIRST: an env whose step_count is 0 has just begun an episode — mg_reset, the same-step reset inside a
+ * step, or the next-step reset call; every other step leaves step_count >= 1 — and seen[b], visits[b] of the launch's agents are
+ * zeroed before the observation is accumulated.  So with a same-step reset the values after a finishing step are those of the
+ * new episode's first observation; with next-step reset the terminal step still accumulates and the reset call clears.
+ * cfg is a view group's config: the launch writes the rows of cfg->view_agent[0 .. n_view) (every agent when n_view == 0) of the
+ * envs with env_mask[b] != 0 (NULL: every env); rows of other agents and of unselected envs are not touched.  One launch, no
+ * atomics, nothing the host has to read; every size mg_encode_views takes (grids to 255 x 255, views to MG_MAX_VIEW).
+ * MG_E_ARG: what mg_encode_views answers it for, or a NULL array. */
+int32_t mg_explore_update(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, uint8_t* seen, int32_t* visits,
+                          int32_t* new_cells, int32_t* visit_count, void* stream);
 
 /* actions: device [B][n_agents], element size `action_bytes` in {1,4,8} (little-endian ints).
  * rewards: device float32 [B][n_agents].  Sets st->done[b].

@@ -149,7 +149,8 @@ SYMBOLS = ["mg_abi_version", "mg_struct_sizes", "mg_host_flag_alloc", "mg_host_f
            "mg_level_seed", "mg_level_apply", "mg_level_apply_rows",
            "mg_goal_distance", "mg_goal_distance_path",
            "mg_solve_distance", "mg_solve_distance_lds_bytes",
-           "mg_fork_rows", "mg_rollout"]
+           "mg_fork_rows", "mg_rollout",
+           "mg_explore_update"]
 
 _lib = None
 _path = LIB_PATH
@@ -229,6 +230,8 @@ def lib():
     # (cfg, src, dst, src_of_dst, dst_of_row, dst_B, R, m, stream) / (cfg, st, actions, action_bytes, T, m, rewards, done, errors, stream)
     L.mg_fork_rows.argtypes = [C.POINTER(Config), C.POINTER(State), C.POINTER(State), vp, vp, i32, i32, i32, vp]
     L.mg_rollout.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, i32, i32, vp, vp, vp, vp]
+    # (cfg, st, env_mask, seen, visits, new_cells, visit_count, stream)
+    L.mg_explore_update.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp, vp, vp, vp, vp]
     L.mg_reset.argtypes = [C.POINTER(Config), C.POINTER(State), C.POINTER(GenProgram), vp, vp]
     L.mg_step.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp]
     L.mg_step_render.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp]

@@ -37,6 +37,7 @@ from . import per_env, rendering, seeding, spaces
 from .agents import GridAgentInterface
 from .gen_edits import EditTable
 from .gen_params import ParamTable
+from .explore import EnvExplore
 from .goal import EnvGoal
 from .lookahead import EnvLookahead
 from .gen_recorder import GenDraw, GenRecorder, _NO_BRANCH, _any_draw, _gen_add, _trace, decode_program, pack_program
@@ -409,7 +410,7 @@ class MultiGridEnv(object):
                  reward_decay=True, seed=1337, respawn=False, ghost_mode=True, agent_spawn_kwargs={},
                  batch_size=1, device=None, seeds=None, auto_reset=False, strict=True, obs_buffers=2,
                  fused_step=True, place_obs=True, encode_in_step=False, obs_format="image", episode_info=False,
-                 obs_delta="auto", specialize=False, specialize_cache=None, level_edits=0, _dry=False):
+                 obs_delta="auto", specialize=False, specialize_cache=None, level_edits=0, explore=False, _dry=False):
         if grid_size is not None:
             assert width is None and height is None
             width, height = grid_size, grid_size
@@ -542,6 +543,12 @@ class MultiGridEnv(object):
         # 0: no table, no op — recordings, programs and launches are what they were
         self._edits = EditTable(self, level_edits)
         self.level_edits = self._edits.K
+        # explore=True: per agent, the world cells its observations have covered this episode (`seen`) and how often it stood
+        # on each cell (`visits`), with the two per-step scalars exploration bonuses are made of (`new_cells`, `visit_count`) —
+        # kept on the device by one more launch behind every reset() and step() (explore.py).  False: nothing is allocated and
+        # nothing is launched
+        self.explore = bool(explore)
+        self._explore = None
         self._spec_ctor = None
         self._spec_last = None
         self._probe = None
@@ -558,6 +565,8 @@ class MultiGridEnv(object):
                 self.device = torch.device("cuda", torch.cuda.current_device())
             self._lib = N.lib()
             self._alloc_state()
+            if self.explore:
+                self._explore = EnvExplore(self)
         self._edits.alloc()
         self._seeds_arg = seeds
         self.seed(seed=seed)
@@ -1117,6 +1126,41 @@ class MultiGridEnv(object):
         registered Goal kinds share (ValueError if they differ or there is none).  Torch ops only."""
         return self._goal.optimal_return(dist)
 
+    # ---- exploration maps (explore=True): None without the option ---------------------------------------------------------
+    @property
+    def seen(self):
+        """(B, n, W, H) bool (uint8 storage), indexed [b, k, x, y] like `goal_distance`'s field: cell (x, y) was inside agent k's
+        view AND VISIBLE in at least one observation returned to the caller since the env's running episode began.  "Visible" is
+        exactly the `vis_mask` of the reference's `gen_obs_grid(agent)` (crop at `get_view_exts`, rotate `dir + 1` times,
+        `process_vis`): all ones with `see_through_walls`, all zeros for a viewer that is not active, clipped to the grid, the
+        transparency that of the grid's own object; `hide_item_types` plays no part; taken on the state the returned observation
+        shows.  ONE OBSERVATION IS ONE UPDATE: every `reset()` and every `step()` updates each env it covers once, after the
+        step's launch (one mg_explore_update launch per view group, on the env's stream, nothing read back) — `reset(env_mask=)`
+        only the selected envs, `step()` every env, one whose episode has ended under `auto_reset=False` included.  A FRESH
+        EPISODE CLEARS FIRST: an env whose step counter is 0 after the launch has just begun an episode (reset(), the same-step
+        reset inside a step, the next-step reset call), and its `seen` and `visits` are cleared before the observation is
+        accumulated — under `auto_reset=True` the values after a finishing step are those of the new episode's first
+        observation; under `"next_step"` the terminal step still accumulates into the finished episode and the reset call
+        clears.  The four tensors are rewritten in place by the next call; `state_dict()` carries `seen` and `visits` (a
+        checkpoint without them loads with cleared maps), `fork` copies the four rows, `lookahead` leaves them alone.
+        `obs_format`, `obs_delta`, `obs_buffers`, `encode_in_step`, `episode_info` and `specialize` do not interact with it."""
+        return None if self._explore is None else self._explore.seen
+
+    @property
+    def visits(self):
+        """(B, n, W, H) int32: the number of those observations (see `seen`) in which agent k was placed on (x, y)"""
+        return None if self._explore is None else self._explore.visits
+
+    @property
+    def new_cells(self):
+        """(B, n) int32: how many cells the last observation added to `seen[b, k]`"""
+        return None if self._explore is None else self._explore.new_cells
+
+    @property
+    def visit_count(self):
+        """(B, n) int32: `visits[b, k]` at agent k's own cell after the last observation's increment; 0 for an agent in no cell"""
+        return None if self._explore is None else self._explore.visit_count
+
     # ---- lookahead: what T steps WOULD return, on a shadow copy of the state --------------------------------------------------
     @_on_device
     def lookahead(self, actions, env_ids=None):
@@ -1427,6 +1471,8 @@ class MultiGridEnv(object):
             else:
                 self.ep_return_t.masked_fill_((self._mask_keep != 0).unsqueeze(1), 0.0)
         self._render()
+        if self._explore is not None:
+            self._explore.update(mask_ptr, stream)
         if self.encode_in_step:
             self._encode_into(self._encoding_buffer())
         if self.strict:
@@ -1479,6 +1525,8 @@ class MultiGridEnv(object):
             self._levels.apply(N.LEVEL_PENDING if self.auto_reset_mode == "next_step" else N.LEVEL_PUBLISH, None, stream)
         r = self._ring[self._ring_i] if self._use_ep else None
         self._launch_step(actions, prog, stream, probe, None if r is None else C.byref(r["ep"]))
+        if self._explore is not None:
+            self._explore.update(None, stream)
         info = {}
         if self.episode_info:
             torch.eq(r["ep_flags"].unsqueeze(0), self._ep_vals, out=r["ep_bits"])
@@ -1788,6 +1836,8 @@ class MultiGridEnv(object):
             sd["params_t"] = self.params_t.clone()
         if self.level_edits:              # the envs' edit lists
             sd["edits_t"] = self.edits_t.clone()
+        if self._explore is not None:     # explore=True: the maps of the running episodes
+            sd.update(self._explore.state())
         if self._levels.on:                     # set_levels: the running episodes' levels, and the seed each env resets to next
             sd["episode_level_t"] = self.episode_level.clone()      # (resolved through the bank now: a bank is no part of a checkpoint)
             sd["level_next_t"] = self._levels.next()
@@ -1807,6 +1857,8 @@ class MultiGridEnv(object):
                 raise ValueError("load_state_dict: level_next_t has shape %s, expected %s" % (tuple(sd["level_next_t"].shape), (self.batch_size,)))
             self._levels.enable()
         want |= levels
+        maps = self._explore.keys_of(sd) if self._explore is not None else set()
+        want |= maps
         if set(sd.keys()) != want:
             raise KeyError("load_state_dict: expected exactly the keys %s, got %s (a checkpoint without "
                            "'version' / 'mt_head' predates the look-ahead RNG form and cannot be resumed)"
@@ -1822,6 +1874,8 @@ class MultiGridEnv(object):
             getattr(self, k).copy_(sd[k])
         if levels:      # in the seeds form: the env's own bank, row b seeded with env b's next level
             self.set_levels(seeds=sd["level_next_t"].to(self.device))
+        if self._explore is not None and not maps:
+            self._explore.clear()
         self.invalidate_obs()
         if bool((self.error_t != 0).any()):
             self._flag._host[0] = 1          # the restored batch carries recorded errors (whatever `strict` is:

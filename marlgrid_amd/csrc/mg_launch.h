@@ -59,4 +59,7 @@ hipError_t launch_fork_rows(const MgConfig& cfg, const MgState& src, const MgSta
                             const int64_t* dst_of_row, int dst_B, int R, int m, hipStream_t s);
 hipError_t launch_rollout(const MgConfig& cfg, const MgState& st, const void* actions, int action_bytes, int T, int m, float* rewards,
                           uint8_t* done, int32_t* errors, hipStream_t s);
+// exploration maps (mg_explore.hip): the seen / visits planes of the config's viewers after one more observation
+hipError_t launch_explore_update(const MgConfig& cfg, const MgState& st, const uint8_t* mask, uint8_t* seen, int32_t* visits,
+                                 int32_t* new_cells, int32_t* visit_count, hipStream_t s);
 }  // namespace mg

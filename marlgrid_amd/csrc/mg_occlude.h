@@ -1,7 +1,16 @@
 // mg_occlude.h — shadow casting (marlgrid/agents.py:298-343) as row bit-masks, shared by the obs
-// raster (mg_render.hip) and the whole-grid frame kernel (mg_frame.hip).
+// raster (mg_render.hip), the whole-grid frame kernel (mg_frame.hip), the encoded views and the exploration maps.
 #pragma once
+// (device code; tests/native also builds it with g++, for mg_explore_core.h: there the qualifiers fall away)
+#if defined(__HIPCC__) || defined(__HIPCC_RTC__)
 #include "mg_device.h"
+#define MG_OCC __device__ __forceinline__
+#define MG_OCC_MEM __device__ inline
+#else
+#include "mg_core.h"
+#define MG_OCC inline
+#define MG_OCC_MEM inline
+#endif
 
 namespace mg {
 
@@ -12,7 +21,7 @@ namespace mg {
 // W: the row width the flood has to cover (the view size when it is a compile-time constant, else
 // MG_MAX_VIEW): log2-many doubling steps — 3 for a 7-wide view, 5 for the 31 columns a 32-bit row mask holds.
 template <int W>
-__device__ __forceinline__ uint32_t flood_right(uint32_t m, uint32_t p) {
+MG_OCC uint32_t flood_right(uint32_t m, uint32_t p) {
     // set bit i+1 whenever bit i is set and p[i] (p = transparency restricted to [ax, vs-2])
     m |= (m & p) << 1;
     uint32_t q = p & (p >> 1);
@@ -32,7 +41,7 @@ __device__ __forceinline__ uint32_t flood_right(uint32_t m, uint32_t p) {
     return m;
 }
 template <int W>
-__device__ __forceinline__ uint32_t flood_left(uint32_t m, uint32_t p) {
+MG_OCC uint32_t flood_left(uint32_t m, uint32_t p) {
     // set bit i-1 whenever bit i is set and p[i] (p = transparency restricted to [1, ax+1])
     m |= (m & p) >> 1;
     uint32_t q = p & (p << 1);
@@ -56,8 +65,7 @@ __device__ __forceinline__ uint32_t flood_left(uint32_t m, uint32_t p) {
 // MG_MAX_VIEW = 31 columns of a 32-bit mask — walk them in memory (occlude_rows_mem)
 constexpr int kRegView = 15;
 template <int VS_>
-__device__ __forceinline__ void occlude_rows(int vs_rt, int off, const uint32_t* __restrict__ T,
-                                             uint32_t* __restrict__ out) {
+MG_OCC void occlude_rows(int vs_rt, int off, const uint32_t* __restrict__ T, uint32_t* __restrict__ out) {
     const int VS = VS_ ? VS_ : vs_rt;
     constexpr int N = VS_ ? VS_ : kRegView;
     const int ax = VS / 2, ay = VS - 1 - off;
@@ -103,7 +111,7 @@ __device__ __forceinline__ void occlude_rows(int vs_rt, int off, const uint32_t*
 
 // The same cast with the rows where they are: T[VS] the transparency rows (read only), M[VS] the result (any memory that is
 // not T: LDS in the obs kernel, a local array in the frame kernel) — plain loops, no register arrays: view sizes 16 .. 31.
-__device__ inline void occlude_rows_mem(int VS, int off, const uint32_t* T, uint32_t* M) {
+MG_OCC_MEM void occlude_rows_mem(int VS, int off, const uint32_t* T, uint32_t* M) {
     const int ax = VS / 2, ay = VS - 1 - off;
     const uint32_t full = (1u << VS) - 1u;
     const uint32_t hi = full & ~((1u << ax) - 1u);            // columns ax .. VS-1

@@ -168,4 +168,6 @@ class EnvLookahead(object):
             if t is not None:
                 put(t)
         env._levels.fork(put)       # set_levels: the running episode's level, and the level the env resets to next
+        if env._explore is not None:
+            env._explore.fork(put)  # explore=True: the four rows of the maps
         env.invalidate_obs()

@@ -62,7 +62,7 @@ def _engine_version():
 def merge_state_dicts(dicts):
     """`MultiGridEnv.state_dict()`s of consecutive slices of a batch -> the state_dict of the whole batch: every tensor
     concatenated along dim 0 in the order given, `version` checked (equal everywhere, and the one this engine reads).  The
-    optional keys (`prestige_t`, `ep_return_t`, `params_t`, `edits_t`, and `episode_level_t` with `level_next_t`) are in every dict or in none: anything else raises KeyError.  Pure: no
+    optional keys (`prestige_t`, `ep_return_t`, `params_t`, `edits_t`, `seen` with `visits`, and `episode_level_t` with `level_next_t`) are in every dict or in none: anything else raises KeyError.  Pure: no
     device is touched beyond what torch.cat does with the tensors it is given (all on one device)."""
     import torch
     dicts = list(dicts)
@@ -382,6 +382,12 @@ class _Shards(object):
             raise NotImplementedError("fork: env %d is on shard %d and env %d on shard %d; a copy stays within one shard"
                                       % (src[i], ks[i], dst[i], kd[i]))
         self._each(lambda k, env: env.fork(src[ks == k] - los[k], dst[kd == k] - los[k]) if (ks == k).any() else None)
+
+    # explore=True: per shard, its env's exploration tensors (None without the option)
+    seen = property(lambda self: [env.seen for env in self.envs])
+    visits = property(lambda self: [env.visits for env in self.envs])
+    new_cells = property(lambda self: [env.new_cells for env in self.envs])
+    visit_count = property(lambda self: [env.visit_count for env in self.envs])
 
     @property
     def solve_exact(self):

@@ -35,6 +35,7 @@
  *                   MultiGridEnv.step calls WOULD return, the env untouched)
  *   mg_explore_update  (none either: per agent, the world cells its observations have covered this episode and how often it
  *                   stood on each cell — what count-based exploration bonuses are made of)
+ *   mg_memory_update   (none either: mg_explore_update, and per agent what each cell showed when it was last seen, and when)
  *   mg_put_obj      MultiGridEnv.put_obj (base.py:655-662)
  *   mg_place        MultiGridEnv.place_obj / try_place_obj outside _gen_grid (base.py:664-708)
  *   mg_render_frame MultiGridEnv.render's whole-grid image: MultiGrid.render(top_agent=None) +
@@ -463,6 +464,25 @@ int32_t mg_rollout(const MgConfig* cfg, const MgState* st, const void* actions, 
  * MG_E_ARG: what mg_encode_views answers it for, or a NULL array. */
 int32_t mg_explore_update(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, uint8_t* seen, int32_t* visits,
                           int32_t* new_cells, int32_t* visit_count, void* stream);
+
+/* Memory maps (no reference counterpart): mg_explore_update, and with it each agent's LAST VIEW OF EVERY CELL.  A caller that
+ * keeps them calls this INSTEAD OF mg_explore_update, at the same places (after every mg_reset with its mask, after every step
+ * launch with NULL): one launch, the view chain run once.  seen, visits, new_cells, visit_count: exactly as mg_explore_update
+ * leaves them.  Two more caller-owned device arrays:
+ *   memory     uint8 [B][n_agents][W][H][4], 4-byte aligned, index [b][k][x][y] = (type, colour, state, known): the first three
+ *              bytes are the triple cell (x, y) had in the most recent observation of agent k in which the cell was inside its
+ *              view AND VISIBLE — byte for byte what mg_encode_views writes at the view cell that maps to (x, y) on the same
+ *              state: the shadow cast applied, hide_item_types applied (a hidden object shows the agent on it or (0, 0, 0)), an
+ *              agent standing there encoded as (agent type, its colour, its heading); known = 1 once the cell has been seen this
+ *              episode, so a seen empty cell (0, 0, 0, 1) differs from a cell never seen (0, 0, 0, 0)
+ *   seen_step  int32 [B][n_agents][W][H]: st->step_count[b] at that most recent observation; -1 where the cell was never seen
+ * The rules are mg_explore_update's: an env whose step_count is 0 is cleared first (memory to 0, seen_step to -1); an inactive
+ * viewer sees nothing and changes nothing, what it remembered stays; the launch writes the rows of cfg's viewers in the selected
+ * envs only.  After every call memory[..][3] == seen, (seen_step >= 0) == seen, and every cell visible in the observation has
+ * seen_step == step_count[b].  No atomics (a view map is injective, two pairs never share a plane), nothing read back.
+ * MG_E_ARG: what mg_explore_update answers it for, a NULL array, or a `memory` that is not 4-byte aligned. */
+int32_t mg_memory_update(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, uint8_t* seen, int32_t* visits,
+                         int32_t* new_cells, int32_t* visit_count, uint8_t* memory, int32_t* seen_step, void* stream);
 
 /* actions: device [B][n_agents], element size `action_bytes` in {1,4,8} (little-endian ints).
  * rewards: device float32 [B][n_agents].  Sets st->done[b].

@@ -150,7 +150,7 @@ SYMBOLS = ["mg_abi_version", "mg_struct_sizes", "mg_host_flag_alloc", "mg_host_f
            "mg_goal_distance", "mg_goal_distance_path",
            "mg_solve_distance", "mg_solve_distance_lds_bytes",
            "mg_fork_rows", "mg_rollout",
-           "mg_explore_update"]
+           "mg_explore_update", "mg_memory_update"]
 
 _lib = None
 _path = LIB_PATH
@@ -232,6 +232,8 @@ def lib():
     L.mg_rollout.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, i32, i32, vp, vp, vp, vp]
     # (cfg, st, env_mask, seen, visits, new_cells, visit_count, stream)
     L.mg_explore_update.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp, vp, vp, vp, vp]
+    # (cfg, st, env_mask, seen, visits, new_cells, visit_count, memory, seen_step, stream)
+    L.mg_memory_update.argtypes = [C.POINTER(Config), C.POINTER(State), vp, vp, vp, vp, vp, vp, vp, vp]
     L.mg_reset.argtypes = [C.POINTER(Config), C.POINTER(State), C.POINTER(GenProgram), vp, vp]
     L.mg_step.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp]
     L.mg_step_render.argtypes = [C.POINTER(Config), C.POINTER(State), vp, i32, vp, C.POINTER(GenProgram), vp, vp]

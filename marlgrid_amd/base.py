@@ -410,7 +410,7 @@ class MultiGridEnv(object):
                  reward_decay=True, seed=1337, respawn=False, ghost_mode=True, agent_spawn_kwargs={},
                  batch_size=1, device=None, seeds=None, auto_reset=False, strict=True, obs_buffers=2,
                  fused_step=True, place_obs=True, encode_in_step=False, obs_format="image", episode_info=False,
-                 obs_delta="auto", specialize=False, specialize_cache=None, level_edits=0, explore=False, _dry=False):
+                 obs_delta="auto", specialize=False, specialize_cache=None, level_edits=0, explore=False, memory=False, _dry=False):
         if grid_size is not None:
             assert width is None and height is None
             width, height = grid_size, grid_size
@@ -547,7 +547,10 @@ class MultiGridEnv(object):
         # on each cell (`visits`), with the two per-step scalars exploration bonuses are made of (`new_cells`, `visit_count`) —
         # kept on the device by one more launch behind every reset() and step() (explore.py).  False: nothing is allocated and
         # nothing is launched
-        self.explore = bool(explore)
+        # memory=True: beside those, each agent's last view of every cell (`memory`) and when it had it (`seen_step`), written
+        # by the same one launch (mg_memory_update instead of mg_explore_update).  It implies explore=True
+        self._memory_on = bool(memory)
+        self.explore = bool(explore) or self._memory_on
         self._explore = None
         self._spec_ctor = None
         self._spec_last = None
@@ -566,7 +569,7 @@ class MultiGridEnv(object):
             self._lib = N.lib()
             self._alloc_state()
             if self.explore:
-                self._explore = EnvExplore(self)
+                self._explore = EnvExplore(self, memory=self._memory_on)
         self._edits.alloc()
         self._seeds_arg = seeds
         self.seed(seed=seed)
@@ -1160,6 +1163,31 @@ class MultiGridEnv(object):
     def visit_count(self):
         """(B, n) int32: `visits[b, k]` at agent k's own cell after the last observation's increment; 0 for an agent in no cell"""
         return None if self._explore is None else self._explore.visit_count
+
+    # ---- memory maps (memory=True, which implies explore=True): None without the option -------------------------------------
+    @property
+    def memory(self):
+        """(B, n, W, H, 4) uint8, indexed [b, k, x, y] = (type, colour, state, known): the triple cell (x, y) had in the most
+        recent observation of agent k in which the cell was inside its view AND VISIBLE (see `seen`) — byte for byte the triple
+        `obs_format="encoded"` shows at the view cell that maps to (x, y): the shadow cast applied, `hide_item_types` applied,
+        an agent standing there encoded with its colour and heading.  `known` is 1 once the cell has been seen this episode: a
+        seen empty cell is (0, 0, 0, 1), a cell never seen (0, 0, 0, 0); `memory[..., 3] == seen` after every call.  The rules
+        are `seen`'s: one observation is one update (every `reset()` for the envs it selects, every `step()` for every env,
+        ONE mg_memory_update launch per view group in place of mg_explore_update, nothing read back); an env whose step counter
+        is 0 after the launch has just begun an episode and is cleared first (`memory` to 0, `seen_step` to -1); an inactive
+        viewer sees nothing and changes nothing, and what it remembered earlier in the episode stays.  Rewritten in place by
+        the next call; `state_dict()` carries `memory` and `seen_step` (a memory=True env that loads a checkpoint without them
+        clears all six maps), `fork` copies the rows, `lookahead` leaves them alone.  An env WITHOUT the option does not take
+        the two keys: `load_state_dict` raises KeyError for them, as an env without `explore` does for `seen` and `visits` — so
+        an explore=True env cannot load a memory=True env's checkpoint unless the caller drops `memory` and `seen_step` first."""
+        return None if self._explore is None else self._explore.memory
+
+    @property
+    def seen_step(self):
+        """(B, n, W, H) int32: the env's `step_count` at that most recent observation (see `memory`), -1 where the cell was
+        never seen this episode: `(seen_step >= 0) == seen`, every cell visible in the observation just returned has
+        `seen_step == step_count[b]`, and `step_count[b] - seen_step` is how stale the memory of a cell is"""
+        return None if self._explore is None else self._explore.seen_step
 
     # ---- lookahead: what T steps WOULD return, on a shadow copy of the state --------------------------------------------------
     @_on_device
@@ -1874,7 +1902,7 @@ class MultiGridEnv(object):
             getattr(self, k).copy_(sd[k])
         if levels:      # in the seeds form: the env's own bank, row b seeded with env b's next level
             self.set_levels(seeds=sd["level_next_t"].to(self.device))
-        if self._explore is not None and not maps:
+        if self._explore is not None and not self._explore.complete(maps):      # (all of them: the invariants between them hold)
             self._explore.clear()
         self.invalidate_obs()
         if bool((self.error_t != 0).any()):

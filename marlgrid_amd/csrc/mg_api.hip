@@ -258,6 +258,15 @@ int32_t mg_explore_update(const MgConfig* cfg, const MgState* st, const uint8_t*
     return rc(mg::launch_explore_update(*cfg, *st, env_mask, seen, visits, new_cells, visit_count, (hipStream_t)stream));
 }
 
+int32_t mg_memory_update(const MgConfig* cfg, const MgState* st, const uint8_t* env_mask, uint8_t* seen, int32_t* visits,
+                         int32_t* new_cells, int32_t* visit_count, uint8_t* memory, int32_t* seen_step, void* stream) {
+    const int e = check_both(cfg, st);
+    if (e) return e;
+    if (!seen || !visits || !new_cells || !visit_count || !memory || !seen_step) return MG_E_ARG;
+    return rc(mg::launch_memory_update(*cfg, *st, env_mask, seen, visits, new_cells, visit_count, memory, seen_step,
+                                       (hipStream_t)stream));
+}
+
 int32_t mg_episode_struct_size(void) { return (int32_t)sizeof(MgEpisode); }
 
 int32_t mg_step_ep(const MgConfig* cfg, const MgState* st, const void* actions, int32_t action_bytes, float* rewards,

@@ -20,6 +20,7 @@
 #include "mg_device.h"
 #include "mg_launch.h"
 #include "mg_occlude.h"
+#include "mg_view_triple.h"
 
 namespace mg {
 
@@ -30,8 +31,6 @@ struct EncViewsLaunch {
     int32_t stage_off;  // LDS byte offset of the run's output image (16-aligned)
     long long pairs;    // B * nv
 };
-
-constexpr int kEvTab = 256 * 4 * 2;          // triples + see_behind bit, hide_item_types masks
 
 // mg_step_encode_views in ONE launch (STEP_ = true): the workgroup first steps its own envs — PB / nv whole envs, one lane
 // per env, mg_core.h's step_load / step_run on [item][lane] LDS columns as step_kernel runs them, auto-reset included — and
@@ -79,17 +78,9 @@ __global__ __launch_bounds__(kBlock) void encode_views_kernel(MgConfig cfg, cons
     const int ne = (int)((p0 + cnt - 1) / nv - b0) + 1;
 
     // A. tables and records
-    for (int o = tid; o < 256; o += kBlock) {
-        uint32_t t = 0, hb = 0;
-        if (o < cfg.n_obj) {
-            const MgObjDesc d = cfg.obj[o];
-            t = (uint32_t)d.type_idx | ((uint32_t)d.color_idx << 8) | ((uint32_t)d.state << 16) |
-                ((d.flags & MG_OF_SEE_BEHIND) ? 1u << 24 : 0u);
-            if (cfg.any_hide && cfg.hide_by_obj) hb = cfg.hide_by_obj[o];
-        }
-        if (o == 0) t = 1u << 24;                                              // None: (0, 0, 0), transparent (base.py:103-106)
-        s_tab[o] = t;
-        s_hide[o] = hb;
+    for (int o = tid; o < 256; o += kBlock) {      // (mg_view_triple.h)
+        s_tab[o] = view_triple_entry(cfg, o);
+        s_hide[o] = view_hide_entry(cfg, o);
     }
     for (int i = tid; i < ne * n; i += kBlock) s_rec[i] = agents[(size_t)b0 * n + i];
     __syncthreads();
@@ -148,10 +139,8 @@ __global__ __launch_bounds__(kBlock) void encode_views_kernel(MgConfig cfg, cons
     }
     __syncthreads();
 
-    // E. the triples, one lane per view row.  A cell's occupant as grid.get returns it: the object; on an empty cell the
-    //    lowest-rank agent standing there (the cell object, base.py:547-552) — an agent on an object is not encoded.
-    //    hide_item_types (base.py:441-449): a hidden object becomes its agents[0] (the lowest-rank agent on it) or None; a
-    //    hidden agent that is not the viewer becomes ITS agents[0] (the second-lowest rank of the cell) or None.
+    // E. the triples, one lane per view row: each visible in-grid cell's occupant as grid.get returns it after
+    //    hide_item_types (view_cell_triple, mg_view_triple.h)
     const int ph = (int)((reinterpret_cast<uintptr_t>(out) + (size_t)p0 * 3 * VV) & 15);
     for (int it = tid; it < rows; it += kBlock) {
         const int t = it / VS, vb = it - t * VS;
@@ -165,29 +154,7 @@ __global__ __launch_bounds__(kBlock) void encode_views_kernel(MgConfig cfg, cons
             uint32_t trip = 0;
             int wx, wy;
             const int c = world_cell(aff, va, vb, wx, wy);
-            if (((vis >> va) & 1u) && c >= 0) {
-                const uint32_t base = g[c];
-                const bool hid_obj = base != 0 && ((s_hide[base] >> k) & 1u);
-                if (base != 0 && !hid_obj) trip = s_tab[base] & 0xFFFFFFu;
-                else {
-                    // the lowest- and second-lowest-rank agents of the cell
-                    const uint32_t cxy = (uint32_t)wx | ((uint32_t)wy << 8);
-                    uint32_t r1 = 0x100, r2 = 0x100, a1 = 0xFF, a2 = 0xFF;
-                    for (int j = 0; j < n; j++) {
-                        const uint64_t rj = rec[j];
-                        if ((rec_byte(rj, MG_AG_FLAGS) & MG_AF_PLACED) && rec_xy(rj) == cxy) {
-                            const uint32_t rk = rec_byte(rj, MG_AG_RANK);
-                            if (rk < r1) { r2 = r1; a2 = a1; r1 = rk; a1 = (uint32_t)j; }
-                            else if (rk < r2) { r2 = rk; a2 = (uint32_t)j; }
-                        }
-                    }
-                    uint32_t a = a1;
-                    if (!hid_obj && a1 != 0xFF && a1 != (uint32_t)k && ((cfg.hide_agent_mask >> k) & 1u)) a = a2;
-                    if (a != 0xFF)
-                        trip = (uint32_t)cfg.agent_type_idx | ((uint32_t)cfg.agent_color_idx[a] << 8) |
-                               (rec_byte(rec[a], MG_AG_DIR) << 16);
-                }
-            }
+            if (((vis >> va) & 1u) && c >= 0) trip = view_cell_triple(cfg, s_tab, s_hide, rec, n, k, g[c], wx, wy);
             uint8_t* o = img + (size_t)va * 3 * VS;
             o[0] = (uint8_t)trip;
             o[1] = (uint8_t)(trip >> 8);

@@ -6,9 +6,15 @@
 // The view's map to world cells is mg_core.h's view_map / view_world and the shadow cast mg_occlude.h's, as the encoded-views
 // launch uses them.  A view map is injective, so the rows of one pair touch disjoint cells of the pair's planes, and two pairs
 // never share a plane: plain byte and dword stores, no atomics.
+//
+// mg_memory_update (`mem`, the kernel's MEM_ = true) keeps two more planes per pair beside those: `memory`, one dword per cell
+// — the triple the cell showed in the pair's most recent observation of it (view_cell_triple, mg_view_triple.h: what
+// mg_encode_views writes at the view cell) with known = 1 in the top byte —, and `seen_step`, the env's step count at that
+// observation (-1: never seen).  The bodies below that take them are added to the launch; the others are shared unchanged.
 #pragma once
 #include "mg_core.h"
 #include "mg_occlude.h"
+#include "mg_view_triple.h"
 
 namespace mg {
 
@@ -96,6 +102,35 @@ MG_HD int explore_mark_row(uint8_t* seen_p, uint32_t aff, int vb, uint32_t vis, 
     return fresh;
 }
 
+// Z, with the memory: a fresh pair's `memory` plane cleared to 0 (never seen: (0, 0, 0, 0)) and its `seen_step` plane to -1.
+// One aligned dword per cell in both: plain dword stores, no alignment cases
+MG_HD void explore_clear_memory(uint32_t* memory_p, int32_t* step_p, int cells, int lane, int lanes) {
+    for (int i = lane; i < cells; i += lanes) memory_p[i] = 0u;
+    for (int i = lane; i < cells; i += lanes) step_p[i] = -1;
+}
+
+// E, with the memory: one view row, as explore_mark_row, and each visible in-grid cell remembered: its triple as viewer k's
+// observation shows it | known << 24 in one dword store, the env's step count `sc` in another.  tab / hide: the tables of
+// mg_view_triple.h; rec: the n records of the env; g: its grid
+MG_HD int explore_remember_row(const MgConfig& cfg, const uint32_t* tab, const uint32_t* hide, const uint64_t* rec, int n, int k,
+                               const uint8_t* g, int32_t sc, uint8_t* seen_p, uint32_t* memory_p, int32_t* step_p, uint32_t aff,
+                               int vb, uint32_t vis, int VS, int W, int H) {
+    int fresh = 0;
+    for (int va = 0; va < VS; va++) {
+        int wx, wy;
+        view_world(aff, va, vb, &wx, &wy);
+        if (!((vis >> va) & 1u) || (unsigned)wx >= (unsigned)W || (unsigned)wy >= (unsigned)H) continue;
+        const int c = wx * H + wy;
+        memory_p[c] = view_cell_triple(cfg, tab, hide, rec, n, k, g[c], wx, wy) | (1u << 24);
+        step_p[c] = sc;
+        if (seen_p[c] == 0) {
+            seen_p[c] = 1;
+            fresh++;
+        }
+    }
+    return fresh;
+}
+
 // F. one pair: the agent's own cell counted -> visits there after the increment; 0 for an agent in no cell
 MG_HD int32_t explore_visit(int32_t* visits_p, uint64_t rec, int W, int H) {
     if (!(rec_byte(rec, MG_AG_FLAGS) & MG_AF_PLACED)) return 0;
@@ -119,27 +154,31 @@ struct ExploreScratch {
     uint32_t* aff;      // [PB][2]
     uint32_t* trow;     // [PB][VS] transparency rows; after phase D the rows' counts of new cells
     uint32_t* vis;      // [PB][VS]
+    uint32_t* tab;      // mem: [256] the triple table, and behind it
+    uint32_t* hide;     // mem: [256] the hide table (kEvTab bytes together); both NULL without the memory
 };
-inline size_t explore_lds_bytes(int n_agents, int VS, int PB, int nv) {
+inline size_t explore_lds_bytes(int n_agents, int VS, int PB, int nv, bool mem = false) {
     const int env_cap = (PB - 1) / nv + 2;
-    return 256 + (size_t)env_cap * n_agents * 8 + (size_t)PB * 8 + (size_t)PB * VS * 4 * 2;
+    return 256 + (size_t)env_cap * n_agents * 8 + (size_t)PB * 8 + (size_t)PB * VS * 4 * 2 + (mem ? (size_t)kEvTab : 0);
 }
-MG_HD ExploreScratch explore_scratch(uint8_t* base, int n_agents, int VS, const ExploreLaunch& lc) {
+MG_HD ExploreScratch explore_scratch(uint8_t* base, int n_agents, int VS, const ExploreLaunch& lc, bool mem = false) {
     ExploreScratch s;
     s.see = base;
     s.rec = reinterpret_cast<uint64_t*>(base + 256);
     s.aff = reinterpret_cast<uint32_t*>(s.rec + (size_t)lc.env_cap * n_agents);
     s.trow = s.aff + 2 * (size_t)lc.PB;
     s.vis = s.trow + (size_t)lc.PB * VS;
+    s.tab = mem ? s.vis + (size_t)lc.PB * VS : nullptr;
+    s.hide = mem ? s.tab + 256 : nullptr;
     return s;
 }
 // pairs per workgroup: one lane per pair where the scratch stays within 48 KiB (several workgroups per CU), else halved
-inline ExploreLaunch explore_launch(const MgConfig& cfg, int block) {
+inline ExploreLaunch explore_launch(const MgConfig& cfg, int block, bool mem = false) {
     ExploreLaunch lc;
     lc.nv = cfg.n_view ? cfg.n_view : cfg.n_agents;
     lc.pairs = (long long)cfg.B * lc.nv;
     int PB = block;
-    while (PB > 1 && explore_lds_bytes(cfg.n_agents, cfg.view_size, PB, lc.nv) > 48 * 1024) PB /= 2;
+    while (PB > 1 && explore_lds_bytes(cfg.n_agents, cfg.view_size, PB, lc.nv, mem) > 48 * 1024) PB /= 2;
     lc.PB = PB;
     lc.env_cap = (PB - 1) / lc.nv + 2;
     return lc;

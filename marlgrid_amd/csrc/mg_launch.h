@@ -62,4 +62,7 @@ hipError_t launch_rollout(const MgConfig& cfg, const MgState& st, const void* ac
 // exploration maps (mg_explore.hip): the seen / visits planes of the config's viewers after one more observation
 hipError_t launch_explore_update(const MgConfig& cfg, const MgState& st, const uint8_t* mask, uint8_t* seen, int32_t* visits,
                                  int32_t* new_cells, int32_t* visit_count, hipStream_t s);
+// ... and with them the memory maps: memory u8 [B][n][W][H][4] (4-byte aligned), seen_step i32 [B][n][W][H]
+hipError_t launch_memory_update(const MgConfig& cfg, const MgState& st, const uint8_t* mask, uint8_t* seen, int32_t* visits,
+                                int32_t* new_cells, int32_t* visit_count, uint8_t* memory, int32_t* seen_step, hipStream_t s);
 }  // namespace mg

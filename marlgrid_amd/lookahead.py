@@ -169,5 +169,5 @@ class EnvLookahead(object):
                 put(t)
         env._levels.fork(put)       # set_levels: the running episode's level, and the level the env resets to next
         if env._explore is not None:
-            env._explore.fork(put)  # explore=True: the four rows of the maps
+            env._explore.fork(put)  # explore=True: the four rows of the maps (memory=True: six)
         env.invalidate_obs()

@@ -62,7 +62,7 @@ def _engine_version():
 def merge_state_dicts(dicts):
     """`MultiGridEnv.state_dict()`s of consecutive slices of a batch -> the state_dict of the whole batch: every tensor
     concatenated along dim 0 in the order given, `version` checked (equal everywhere, and the one this engine reads).  The
-    optional keys (`prestige_t`, `ep_return_t`, `params_t`, `edits_t`, `seen` with `visits`, and `episode_level_t` with `level_next_t`) are in every dict or in none: anything else raises KeyError.  Pure: no
+    optional keys (`prestige_t`, `ep_return_t`, `params_t`, `edits_t`, `seen` with `visits`, `memory` with `seen_step`, and `episode_level_t` with `level_next_t`) are in every dict or in none: anything else raises KeyError.  Pure: no
     device is touched beyond what torch.cat does with the tensors it is given (all on one device)."""
     import torch
     dicts = list(dicts)
@@ -388,6 +388,9 @@ class _Shards(object):
     visits = property(lambda self: [env.visits for env in self.envs])
     new_cells = property(lambda self: [env.new_cells for env in self.envs])
     visit_count = property(lambda self: [env.visit_count for env in self.envs])
+    # memory=True: the two memory tensors likewise
+    memory = property(lambda self: [env.memory for env in self.envs])
+    seen_step = property(lambda self: [env.seen_step for env in self.envs])
 
     @property
     def solve_exact(self):
